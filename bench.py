@@ -14,16 +14,29 @@ points the Python quantizers call), with precomputed arguments, on torch's curre
 stream.  HIP events bracket the kernels inside the timed region: their mean gives
 each kernel's duration -> roofline.achieved.
 
-The same JSON line carries, under "configs", the other BASELINE configs measured in
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure needs and
+nothing else: build the workload, warm up, settle the store gates, pick the launch mode,
+time exactly K steps, write the outputs (`--dump-outputs DIR`) and print the JSON line.
+
+`--dump-outputs DIR` writes what the last timed step computed -- the arrays a caller of
+that step receives -- as DIR/<name>.npy (float32 / float64; an array above its share of
+48 MiB is a fixed, seeded sample of its elements).  Inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
+
+`--full` adds every secondary measurement and check to the same JSON line: the self-check
+against the reference's formulas, the timed steps repeated in the other launch mode
+("alt_launch"), under "configs" the other BASELINE configs measured in
 the same run (C1 per-tensor, C3 LSQ, C4 YOLOv8n backbone, C5 calibration) and
 "batched_act_quant" (north_star's batched activation quant: per-call observe with the
 RCCL exchange + fake quant over a 1024-image batch split across the ranks), plus
 "api_us_per_step" (the C2 step through the public Python API), beside
 "api_torch_ref_us_per_step" (torch's own (x * 1.0).backward(g) on the same tensor and
 box) and the learnable per-call step "api_learn_us_per_step" beside torch's x * s
-("api_learn_torch_xs_us_per_step").
+("api_learn_torch_xs_us_per_step"), the C2 forward with codes, the kernels that are not
+part of the step, and the CPU baselines.
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload c1..c5] [--extras LIST]
+  python bench.py [--gpus N --steps K --warmup W] [--workload c1..c5] [--dump-outputs DIR]
+                  [--full [--extras LIST] [--no-api] [--no-cpu-baseline]]
 
 --gpus N > 1 without a torchrun environment: this process (which never touches the
 GPU) starts `torch.distributed.run` with N ranks, one GPU each, RCCL, and exits with
@@ -56,8 +69,13 @@ def parse(argv=None):
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=20)
     p.add_argument("--workload", choices=["c1", "c2", "c3", "c4", "c5", "act"], default="c2")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement and check (self-check, the other launch mode, "
+                        "the other configs, off-step kernels, public-API timings, CPU baselines)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy")
     p.add_argument("--extras", default=None,
-                   help="comma list of extra configs in the same line (c1,c3,c4,c5,act; 'none'); "
+                   help="with --full: comma list of extra configs in the same line (c1,c3,c4,c5,act; 'none'); "
                         "default: all of them for the c2 headline, none otherwise")
     p.add_argument("--batch", type=int, default=256, help="C4 batch (reference: 256)")
     p.add_argument("--bits-w", type=int, default=2, help="C4 weight bits (YAML default 2; SURVEY also w8)")
@@ -88,12 +106,16 @@ def parse(argv=None):
                    help="experiments: vsiq_set_tuning(KEY, VALUE) before the workload is built "
                         "(keys: include/vsiq.h VSIQ_TUNE_*)")
     a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
     if a.extras is None:
-        a.extras = "c1,c3,c4,c5,act" if a.workload == "c2" else ""
+        a.extras = "c1,c3,c4,c5,act" if a.full and a.workload == "c2" else ""
     a.extras = [e for e in a.extras.split(",") if e and e != "none"]
     bad = [e for e in a.extras if e not in EXTRA_STEPS]
     if bad:
         p.error(f"unknown --extras {bad}")
+    if a.extras and not a.full:
+        p.error("--extras runs under --full only")
     return a
 
 
@@ -235,6 +257,13 @@ class C2PerChannel:
             rc |= self.f_bwd(*self.slots[(i0 + j) % ns]["bwd"])
         ev[2].record()
         return rc
+
+    def outputs(self, i):
+        """What step i hands its caller: the fake-quantized weight, the qparams and running
+        min / max of the observer, and the straight-through weight gradient."""
+        s = self.slots[i % len(self.slots)]
+        return {"y": s["y"], "grad_w": s["gx"], "scale": s["scale"], "zero_point": s["zp"],
+                "running_min": s["rmin"], "running_max": s["rmax"]}
 
     def codes_variant(self, groups=25):
         """SURVEY §8d's second C2 figure: the forward with the uint8 codes emitted as well
@@ -402,6 +431,10 @@ class C1PerTensor(C2PerChannel):
         ev[1].record()
         return rc
 
+    def outputs(self, i):
+        s = self.slots[i % len(self.slots)]
+        return {"y": s["y"], "qparams": s["qp"], "running_min_max": s["rmm"]}
+
     def check(self):
         """Slot 0 against the reference's formulas in torch on the host (IEEE fp32 x / s)."""
         s = self.slots[0]
@@ -458,6 +491,10 @@ class C3Lsq(C2PerChannel):
         self.f_fwd = lib.vsiq_fq_fwd_f32
         self.f_bwd = lib.vsiq_lsq_bwd_f32
         self.kernels = {"fq_fwd": 8 * n, "lsq_bwd": 12 * n}
+
+    def outputs(self, i):
+        s = self.slots[i % len(self.slots)]
+        return {"y": s["y"], "grad_x": s["gx"], "qparam_grads": s["grads"]}
 
     def check(self):
         """Slot 0: y and grad_x bit-exact against the reference's formulas in torch on the
@@ -633,6 +670,14 @@ class C4Backbone:
         ev[2].record()
         return rc
 
+    def outputs(self, i):
+        out = {}
+        for j, t in enumerate(self.keep):
+            out.update({f"l{j:02d}_wq": t["wq"], f"l{j:02d}_y": t["y"], f"l{j:02d}_grad_c": t["gc"],
+                        f"l{j:02d}_grad_w": t["gwx"], f"l{j:02d}_qparam_grads_w": t["grads_w"],
+                        f"l{j:02d}_qparam_grads_a": t["grads_a"]})
+        return out
+
     def check(self):
         """Layer 0 (the largest activation): the fused ReLU + act fake quant y bit-exact
         against torch on the host over the first 2M elements; grad zero where the conv
@@ -742,6 +787,11 @@ class C5Calibration:
         self._sync(min(self.steps, i0 + cnt))
         ev[2].record()
         return rc
+
+    def outputs(self, i):
+        out = {f"l{j:02d}_y": y for j, y in enumerate(self.ys)}
+        out["running_min_max"] = torch.stack(self.minmax, dim=-1)
+        return out
 
     def alt_kernels(self, reps=20):
         """The opt-in K2m pass (observe only, 4 B/elem) over the same 27 tensors, event-
@@ -865,6 +915,12 @@ class ActQuant:
             rc |= self.launch(i0 + j)
         ev[1].record()
         return rc
+
+    def outputs(self, i):
+        out = {}
+        for j, t in enumerate(self.L):
+            out.update({f"l{j:02d}_y": t["y"], f"l{j:02d}_qparams": t["qp"]})
+        return out
 
     def check(self):
         """qparams identical on every rank; layer 0's y bit-exact (first 2M elements)
@@ -1196,7 +1252,36 @@ def capture_groups(W, groups, nphase):
     return out
 
 
-def measure(W, steps, warmup, world, graphs=None):
+DUMP_BUDGET = 48 << 20   # bytes of --dump-outputs arrays in all (the .npy headers are on top)
+
+
+def dump_outputs(path, arrays):
+    """The {name: tensor} outputs of one step as path/<name>.npy, float32 (float64 tensors
+    stay float64).  Small arrays are written whole and the rest of the byte budget is shared
+    equally by the others, each written as a sample: the elements at sorted indices drawn
+    (with replacement) by a generator seeded with the array's position, so every run with
+    the same arguments writes the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, share = DUMP_BUDGET, 0
+    sizes = sorted(t.numel() * max(4, t.element_size()) for t in arrays.values())
+    for k, b in enumerate(sizes):   # smallest first: what fits its equal share of the rest is whole
+        share = left // (len(sizes) - k)
+        if b > share:
+            break
+        left -= b
+    for k, (name, t) in enumerate(arrays.items()):
+        t = t.detach().reshape(-1)
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            idx = torch.randint(0, t.numel(), (keep,), generator=torch.Generator().manual_seed(1000 + k))
+            t = t[idx.sort().values.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
+def measure(W, steps, warmup, world, graphs=None, full=True, dump=None):
     """W untimed warmup steps, self-check, then exactly `steps` timed steps between
     barrier + synchronize on both sides; the max over ranks of the wall time; per-phase
     HIP-event durations (rank-local) -> roofline of the dominant phase.
@@ -1209,7 +1294,11 @@ def measure(W, steps, warmup, world, graphs=None):
     fast host (measured: C2 29.7 vs 28.2 us/step).  So an untimed trial (up to 4 groups,
     5 rounds each way, median wall time; one rank: graph unless direct is >1 % faster,
     several: graph only if >1 % faster) picks the mode for the timed region, and the same
-    `steps` are then timed the other way too and reported as "alt_launch"."""
+    `steps` are then timed the other way too and reported as "alt_launch" (full only).
+
+    dump: a directory for the outputs of the last timed step (dump_outputs), written right
+    after the timed steps.  full=False leaves out what the headline figure does not need:
+    the self-check ("self_check" is None) and the alt_launch repetition."""
     for i in range(warmup):
         assert W.launch(i) == 0
     settle, gate_sites = settle_gates(W, world=world)
@@ -1231,12 +1320,15 @@ def measure(W, steps, warmup, world, graphs=None):
         if world > 1:
             use_graph = _agree(use_graph, world)
     dt, evs = _timed(W, groups, names, steps, world, captured if use_graph else None)
-    alt = _timed(W, groups, names, steps, world, None if use_graph else captured) if captured is not None else None
-    out = _report(W, steps, world, dt, _durations(evs, names, steps), names, settle, gate_sites)
+    if dump:
+        dump_outputs(dump, W.outputs(steps - 1))
+    alt = (_timed(W, groups, names, steps, world, None if use_graph else captured)
+           if full and captured is not None else None)
+    out = _report(W, steps, world, dt, _durations(evs, names, steps), names, settle, gate_sites, check=full)
     out["launch"] = "hip graph per phase and group" if use_graph else "direct"
     if alt is not None:
         adt, aevs = alt
-        ar = _report(W, steps, world, adt, _durations(aevs, names, steps), names, settle, gate_sites)
+        ar = _report(W, steps, world, adt, _durations(aevs, names, steps), names, settle, gate_sites, check=True)
         out["alt_launch"] = {"launch": "direct" if use_graph else "hip graph per phase and group",
                              "value": ar["value"], "ms_per_step": ar["ms_per_step"],
                              "frac": ar["roofline"]["frac"],
@@ -1357,15 +1449,15 @@ def _timed(W, groups, names, steps, world, captured):
     return dt, evs
 
 
-def _report(W, steps, world, dt, dur, names, settle, gate_sites):
+def _report(W, steps, world, dt, dur, names, settle, gate_sites, check=True):
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=torch.cuda.current_device())
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     # self-check AFTER the timed region, on the outputs of the timed launches (host work
     # between warmup and timing would leave the GPU idle right before the timed steps)
-    ok = bool(W.check())
-    if world > 1:
+    ok = bool(W.check()) if check else None
+    if check and world > 1:
         t = torch.tensor([int(ok)], device=torch.cuda.current_device())
         dist.all_reduce(t, op=dist.ReduceOp.MIN)
         ok = bool(t.item())
@@ -1608,13 +1700,13 @@ def main(argv=None):
         progress(f"gate table {a.gate_table}: {H.gate_load(a.gate_table)} sites, tuner frozen")
     if a.markers:
         MARKERS.append(True)
-    cpu = rank == 0 and world == 1 and not a.no_cpu_baseline
+    cpu = a.full and rank == 0 and world == 1 and not a.no_cpu_baseline
     bits = (a.bits_w, a.bits_a)
 
     progress(f"{a.workload}: build")
     W = build_workload(a.workload, a, dev, rank, world)
     progress(f"{a.workload}: measure")
-    r = measure(W, a.steps, a.warmup, world)
+    r = measure(W, a.steps, a.warmup, world, full=a.full, dump=a.dump_outputs if rank == 0 else None)
     cfg = describe(W, a.workload, a, world)
     cfg["self_check"] = r["self_check"]
     out = {
@@ -1624,6 +1716,7 @@ def main(argv=None):
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": r["ms_per_step"],
         "higher_is_better": True,
         "scaling": "strong" if a.workload == "act" else "weak",
@@ -1645,14 +1738,14 @@ def main(argv=None):
         out["config"]["tuning"] = a.tune
     if a.gate_table:
         out["store_gate"]["table"] = {"loaded": a.gate_table, "frozen": True}
-    if a.workload == "c2":
+    if a.full and a.workload == "c2":
         progress("c2: forward with uint8 codes")
         out["kernels"]["pc_observe_fq_fwd_with_codes"] = W.codes_variant()
-    if hasattr(W, "alt_kernels"):
+    if a.full and hasattr(W, "alt_kernels"):
         out["kernels"].update(W.alt_kernels())
     del W
     torch.cuda.empty_cache()
-    if a.workload == "c2" and not a.no_api:
+    if a.full and a.workload == "c2" and not a.no_api:
         progress("c2: public API timing")
         r0 = gate_retunes(H)
         out.update(api_timings(dev))

@@ -7,7 +7,7 @@ it, and only as the checker / the timed CPU baseline.  The product package
 
 Parity status: PINNED.  ``fakequant_np`` is checked bit-for-bit against golden
 vectors produced by running the reference itself in the build container
-(``tests/golden/gen_goldens.py`` -> ``tests/golden/fakequant_goldens.npz``),
+(``tests/golden/gen_goldens.py`` -> ``tests/golden/fakequant_goldens_*.npz``),
 see ``tests/test_oracle_golden.py``.
 
 Modules

@@ -689,7 +689,16 @@ cases.append(dict(kind="fuse_structure", patterns=patterns, structure=struct,
                            "^0$": dict(bits_w=3, bits_a=3), "fc": dict(bits_w=8, bits_a=6, a_symmetric=False)},
                   state_dict={k: put("toy_" + k, v) for k, v in toy_sd.items()}))
 
-np.savez_compressed(os.path.join(OUT, "fakequant_goldens.npz"), **arrays)
+# several archives, each well below 1 MiB: a new one once 700 KiB of raw data are in the last
+shards, size = [{}], 0
+for k, v in arrays.items():
+    if shards[-1] and size + v.nbytes > (700 << 10):
+        shards.append({})
+        size = 0
+    shards[-1][k] = v
+    size += v.nbytes
+for i, s in enumerate(shards):
+    np.savez_compressed(os.path.join(OUT, f"fakequant_goldens_{i}.npz"), **s)
 with open(os.path.join(OUT, "cases.json"), "w") as f:
     json.dump({"generator": "tests/golden/gen_goldens.py", "torch": torch.__version__,
                "reference": "tranngocduvnvp/VSIQuantization @ /root/reference", "cases": cases},

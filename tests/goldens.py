@@ -1,4 +1,5 @@
 """Loader + comparison helpers for the reference golden vectors (tests/golden/)."""
+import glob
 import json
 import os
 
@@ -19,8 +20,12 @@ def load():
     if "d" not in _cache:
         with open(os.path.join(GOLDEN_DIR, "cases.json")) as f:
             meta = json.load(f)
-        arrs = np.load(os.path.join(GOLDEN_DIR, "fakequant_goldens.npz"), allow_pickle=False)
-        _cache["d"] = (meta["cases"], {k: arrs[k] for k in arrs.files})
+        arrays = {}   # the arrays are spread over several archives (each below 1 MiB)
+        for path in sorted(glob.glob(os.path.join(GOLDEN_DIR, "fakequant_goldens_*.npz"))):
+            arrs = np.load(path, allow_pickle=False)
+            arrays.update({k: arrs[k] for k in arrs.files})
+        assert arrays, "no tests/golden/fakequant_goldens_*.npz"
+        _cache["d"] = (meta["cases"], arrays)
     return _cache["d"]
 
 

@@ -5,6 +5,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 import bench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,10 +22,41 @@ def test_yolov8n_backbone_matches_survey_c4():
 
 
 def test_parse_extras_defaults():
-    assert bench.parse([]).extras == ["c1", "c3", "c4", "c5", "act"]          # headline C2: all configs
-    assert bench.parse(["--workload", "c3"]).extras == []
+    assert bench.parse(["--full"]).extras == ["c1", "c3", "c4", "c5", "act"]  # headline C2: all configs
+    assert bench.parse(["--full", "--workload", "c3"]).extras == []
+    assert bench.parse(["--full", "--extras", "none"]).extras == []
+    assert bench.parse(["--full", "--extras", "c4,act"]).extras == ["c4", "act"]
+
+
+def test_plain_run_has_no_secondary_legs():
+    """Without --full nothing but the headline workload runs; asking for extras is an error."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.full, a.extras, a.dump_outputs, a.steps, a.warmup) == (False, [], None, 7, 3)
     assert bench.parse(["--extras", "none"]).extras == []
-    assert bench.parse(["--extras", "c4,act"]).extras == ["c4", "act"]
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+    for bad in (["--extras", "c4"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """Small arrays are written whole (float64 stays float64, the rest float32); an array
+    above its share of the budget is the same seeded sample on every call."""
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4096)
+    g = bench.torch.Generator().manual_seed(3)
+    big = bench.torch.randn(50, 100, generator=g)
+    arrays = {"big": big, "qp": bench.torch.arange(4, dtype=bench.torch.float64),
+              "codes": bench.torch.arange(6, dtype=bench.torch.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "codes.npy", "qp.npy"]
+    assert a["qp"].dtype == np.float64 and a["qp"].tolist() == [0.0, 1.0, 2.0, 3.0]
+    assert a["codes"].dtype == np.float32 and a["codes"].tolist() == [0.0, 1.0, 2.0, 3.0, 4.0, 5.0]
+    assert a["big"].dtype == np.float32 and a["big"].size == (4096 - 32 - 24) // 4
+    assert sum(v.nbytes for v in a.values()) <= 4096
+    assert np.isin(a["big"], big.numpy()).all() and len(np.unique(a["big"])) > a["big"].size // 2
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")) for k, v in a.items())
 
 
 def _run(args, env_extra=None):

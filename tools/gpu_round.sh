@@ -16,5 +16,5 @@ run smoke 600 python -u -c "import __graft_entry__ as g; g.smoke()" || exit $?
 run pytest_gpu "${PYTEST_TIMEOUT:-900}" python -u -m pytest tests -m gpu -x -q ${PYTEST_ARGS:-}
 rc=$?
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
-run bench 600 python -u bench.py ${BENCH_ARGS:-} || exit $?
+run bench 600 python -u bench.py --full ${BENCH_ARGS:-} || exit $?
 exit 0
