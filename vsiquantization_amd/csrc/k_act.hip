@@ -4,7 +4,7 @@
 // backward.  Same element code as K5 (vsiq_common.cuh): SiLU bit for bit as torch's CPU
 // kernel on the reference host, so a calibration forward hands the next layer the
 // reference's activations, not torch's HIP silu (a different exp).
-#include "vsiq_common.cuh"
+#include "dispatch.cuh"
 
 namespace vsiq {
 
@@ -31,22 +31,6 @@ __global__ __launch_bounds__(kBlock) void k_act(const float *__restrict__ g, con
     if (base + u * kBlock < ng) store_group<VEC, NT>(y, base + u * kBlock, n, o[u]);
 }
 
-template <int ACT>
-void launch_act(bool vec, bool nt, bool bwd, const float *g, const float *c, float *y, int64_t n,
-                const SiluLay &L, hipStream_t st) {
-  const dim3 grid((unsigned)oneshot_grid(cdiv(n, 4)));
-#define KA(V, T, B) hipLaunchKernelGGL((k_act<V, T, ACT, B>), grid, dim3(kBlock), 0, st, g, c, y, n, L)
-  if (bwd) {
-    if (vec && nt) KA(true, true, true);
-    else if (vec) KA(true, false, true);
-    else KA(false, false, true);
-  } else {
-    if (vec && nt) KA(true, true, false);
-    else if (vec) KA(true, false, false);
-    else KA(false, false, false);
-  }
-#undef KA
-}
 
 // exp self-test: both exps of the SiLU element code (Sleef's vectorized expf, glibc's
 // scalar expf) for arbitrary inputs, checked bitwise against the oracle's restatement
@@ -65,8 +49,16 @@ int act_run(const float *g, const float *c, float *y, int64_t n, int act, bool b
   if (!c || !y || (bwd && !g)) return VSIQ_E_ARG;
   if (oneshot_grid(cdiv(n, 4)) > 0x7fffffffLL) return VSIQ_E_ARG;
   const bool vec = n % 4 == 0 && aligned16(c) && aligned16(y) && (!bwd || aligned16(g));
-  VSIQ_ACT(act, launch_act, vec, g_tune.nontemporal != 0, bwd, g, c, y, n, act_lay(act, n),
-           (hipStream_t)stream);
+  const SiluLay L = act_lay(act, n);
+  const dim3 grid((unsigned)oneshot_grid(cdiv(n, 4)));
+  with_act(act, [&](auto A) {
+    with_bool(bwd, [&](auto B) {
+      with_vec_nt(vec, g_tune.nontemporal != 0, [&](auto V, auto N) {
+        hipLaunchKernelGGL((k_act<decltype(V)::value, decltype(N)::value, decltype(A)::value, decltype(B)::value>), grid,
+                           dim3(kBlock), 0, (hipStream_t)stream, g, c, y, n, L);
+      });
+    });
+  });
   return launch_rc();
 }
 

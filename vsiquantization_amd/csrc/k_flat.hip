@@ -1,6 +1,7 @@
 // k_flat.hip — K2 per-tensor observer (optionally over a fused ReLU/SiLU), the
 // division / fast-path self-tests, and the library-level C ABI entry points
 // (K1 lives in k_fq.hip, K4 in k_lsq.hip, the STE backward in k_ste.hip).
+#include "dispatch.cuh"
 #include "k_body.cuh"   // K1 block body (K9); includes vsiq_common.cuh
 
 namespace vsiq {
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(kBlock) void k_observe(const float *__restrict__ x,
 // A pure read (no stores share vmcnt with the loads), latency hidden by the other
 // waves of the CU.  Fewer, longer-lived workgroups than the one-shot form: fewer
 // partial records to fold and arrivals to serialize (MI355X, C5 layer sizes:
-// 52M elements 53.2 -> 38.6 us, 1.6M 10.1 -> 9.4 us; tools/exp/obs_bench.py).
+// 52M elements 53.2 -> 38.6 us, 1.6M 10.1 -> 9.4 us).
 template <bool VEC, bool NT, int ACT, int U>
 __global__ __launch_bounds__(kBlock) void k_observe_loop(const float *__restrict__ x, int64_t n,
                                                           double *__restrict__ stats_out,
@@ -210,8 +211,7 @@ __global__ __launch_bounds__(kBlock) void k_observe_loop(const float *__restrict
 }
 
 // One K2p record per WAVE (DPP reductions only): no LDS round trip and no barrier in
-// the tail of the grid (C5 observe phase 263 -> 253-258 us on MI355X,
-// tools/exp/floor_bench.py).  Record {min, max, nan count, sum|x|, sum x, sum x^2, n,
+// the tail of the grid (C5 observe phase 263 -> 253-258 us on MI355X).  Record {min, max, nan count, sum|x|, sum x, sum x^2, n,
 // records} of wave w of block blk.
 __device__ __forceinline__ void store_part_record(ObsAcc &a, double *__restrict__ parts, int64_t blk,
                                                   int64_t nblk, int64_t n) {
@@ -445,23 +445,23 @@ __global__ __launch_bounds__(kSmallBlock) void k_observe_fq_small(
   }
 }
 
-template <bool VEC, bool NT, int ACT>
-void launch_observe_fq_small(const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n, double *st,
-                             float *run, double *qp, int sym, double qden, double eps, float lo, float hi,
-                             const SiluLay &L, hipStream_t s) {
+void launch_observe_fq_small(int act, bool vec, bool nt, const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n,
+                             double *st, float *run, double *qp, int sym, double qden, double eps, float lo, float hi,
+                             hipStream_t s) {
+  const SiluLay L = act_lay(act, n);
   // groups per lane: 2 up to 8192 elements (no clamped duplicate loads), else 16
-#define K8(MASK, CODES)                                                                                    \
-  if (n <= (int64_t)kSmallBlock * 2 * 4)                                                                   \
-    hipLaunchKernelGGL((k_observe_fq_small<VEC, NT, ACT, MASK, CODES, 2>), dim3(1), dim3(kSmallBlock), 0, s, x, \
-                       y, c, m, n, st, run, qp, sym, qden, eps, lo, hi, L);                                    \
-  else                                                                                                     \
-    hipLaunchKernelGGL((k_observe_fq_small<VEC, NT, ACT, MASK, CODES, kSmallGroups>), dim3(1), dim3(kSmallBlock), \
-                       0, s, x, y, c, m, n, st, run, qp, sym, qden, eps, lo, hi, L)
-  if (m && c) { K8(true, true); }
-  else if (m) { K8(true, false); }
-  else if (c) { K8(false, true); }
-  else { K8(false, false); }
-#undef K8
+  const int u = n <= (int64_t)kSmallBlock * 2 * 4 ? 2 : kSmallGroups;
+  with_act(act, [&](auto A) {
+    with_vec_nt(vec, nt, [&](auto V, auto N) {
+      with_bool2(m != nullptr, c != nullptr, [&](auto M, auto C) {
+        with_int<2, kSmallGroups>(u, [&](auto U) {
+          hipLaunchKernelGGL((k_observe_fq_small<decltype(V)::value, decltype(N)::value, decltype(A)::value,
+                                                 decltype(M)::value, decltype(C)::value, decltype(U)::value>),
+                             dim3(1), dim3(kSmallBlock), 0, s, x, y, c, m, n, st, run, qp, sym, qden, eps, lo, hi, L);
+        });
+      });
+    });
+  });
 }
 
 // ----------------------------------------------------------------------------
@@ -484,7 +484,12 @@ constexpr int64_t kFoldFqMax = (int64_t)1 << 18;   // largest n (fq grid <= 128 
 
 template <int ACT, int U>
 void launch_observe_part_u(bool vec, bool nt, const float *x, int64_t n, double *parts, int64_t grid,
-                           const SiluLay &L, hipStream_t st);   // K2p launch, below
+                           const SiluLay &L, hipStream_t st) {   // K2p launch at U groups per lane per step
+  with_vec_nt(vec, nt, [&](auto V, auto N) {
+    hipLaunchKernelGGL((k_observe_part<decltype(V)::value, decltype(N)::value, ACT, U>), dim3((unsigned)grid),
+                       dim3(kBlock), 0, st, x, n, parts, L);
+  });
+}
 
 inline int64_t fold_fq_part_grid(int64_t n) {
   const int64_t units = cdiv(cdiv(n, 4), (int64_t)kBlock);
@@ -540,27 +545,23 @@ __global__ __launch_bounds__(kBlock) void k_fold_fq_fwd(
   fq_fwd_block<VEC, NT, CODES, MASK, ACT, kFlatU>(x, y, codes, mask, n, p, blockIdx.x, GateClk{0}, 0u, L);
 }
 
-template <int ACT>
-void launch_fold_fq_act(bool vec, bool nt, const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n,
-                        double *parts, double *st, float *run, double *qp, int sym, double qden, double eps,
-                        float lo, float hi, const SiluLay &L, hipStream_t s) {
+void launch_fold_fq(int act, bool vec, bool nt, const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n,
+                    double *parts, double *st, float *run, double *qp, int sym, double qden, double eps, float lo,
+                    float hi, hipStream_t s) {
+  const SiluLay L = act_lay(act, n);
   const int64_t pgrid = fold_fq_part_grid(n);
-  launch_observe_part_u<ACT, kFoldFqU>(vec, nt, x, n, parts, pgrid, L, s);
   const int nrec = (int)(pgrid * kWaves);
   const dim3 grid((unsigned)oneshot_grid(cdiv(n, 4)));
-#define K9(V, T, C, M)                                                                                       \
-  hipLaunchKernelGGL((k_fold_fq_fwd<V, T, C, M, ACT>), grid, dim3(kBlock), 0, s, x, y, c, m, n, parts, nrec, st, \
-                     run, qp, sym, qden, eps, lo, hi, L)
-#define K9CM(V, T)                  \
-  if (c && m) { K9(V, T, true, true); }        \
-  else if (c) { K9(V, T, true, false); }       \
-  else if (m) { K9(V, T, false, true); }       \
-  else { K9(V, T, false, false); }
-  if (vec && nt) { K9CM(true, true) }
-  else if (vec) { K9CM(true, false) }
-  else { K9CM(false, false) }
-#undef K9CM
-#undef K9
+  with_act(act, [&](auto A) {
+    launch_observe_part_u<decltype(A)::value, kFoldFqU>(vec, nt, x, n, parts, pgrid, L, s);
+    with_vec_nt(vec, nt, [&](auto V, auto N) {
+      with_bool2(c != nullptr, m != nullptr, [&](auto C, auto M) {
+        hipLaunchKernelGGL((k_fold_fq_fwd<decltype(V)::value, decltype(N)::value, decltype(C)::value,
+                                          decltype(M)::value, decltype(A)::value>),
+                           grid, dim3(kBlock), 0, s, x, y, c, m, n, parts, nrec, st, run, qp, sym, qden, eps, lo, hi, L);
+      });
+    });
+  });
 }
 
 // ----------------------------------------------------------------------------
@@ -721,29 +722,23 @@ inline int observe_fq_grid_steps(int64_t n) {
   return cdiv(cdiv(n, 4), fold_fq_part_grid(n) * kBlock * kFoldFqU) <= 1 ? 1 : 2;
 }
 
-template <int ACT>
-void launch_observe_fq_grid_act(bool vec, bool nt, const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n,
-                                double *parts, uint32_t *counter, double *st, float *run, double *qp, int sym,
-                                double qden, double eps, float lo, float hi, const SiluLay &L, hipStream_t s) {
+void launch_observe_fq_grid(int act, bool vec, bool nt, const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n,
+                            double *parts, uint32_t *counter, double *st, float *run, double *qp, int sym,
+                            double qden, double eps, float lo, float hi, hipStream_t s) {
+  const SiluLay L = act_lay(act, n);
   const dim3 grid((unsigned)fold_fq_part_grid(n));
-  const int steps = observe_fq_grid_steps(n);
-#define K10(V, T, C, M, S_)                                                                                      \
-  hipLaunchKernelGGL((k_observe_fq_grid<V, T, C, M, ACT, S_>), grid, dim3(kBlock), 0, s, x, y, c, m, n, parts, \
-                     counter, st, run, qp, sym, qden, eps, lo, hi, L)
-#define K10S(V, T, C, M)                \
-  if (steps == 1) { K10(V, T, C, M, 1); } \
-  else { K10(V, T, C, M, 2); }
-#define K10CM(V, T)                             \
-  if (c && m) { K10S(V, T, true, true) }        \
-  else if (c) { K10S(V, T, true, false) }       \
-  else if (m) { K10S(V, T, false, true) }       \
-  else { K10S(V, T, false, false) }
-  if (vec && nt) { K10CM(true, true) }
-  else if (vec) { K10CM(true, false) }
-  else { K10CM(false, false) }
-#undef K10CM
-#undef K10S
-#undef K10
+  with_act(act, [&](auto A) {
+    with_vec_nt(vec, nt, [&](auto V, auto N) {
+      with_bool2(c != nullptr, m != nullptr, [&](auto C, auto M) {
+        with_int<1, 2>(observe_fq_grid_steps(n), [&](auto S) {
+          hipLaunchKernelGGL((k_observe_fq_grid<decltype(V)::value, decltype(N)::value, decltype(C)::value,
+                                                decltype(M)::value, decltype(A)::value, decltype(S)::value>),
+                             grid, dim3(kBlock), 0, s, x, y, c, m, n, parts, counter, st, run, qp, sym, qden, eps, lo,
+                             hi, L);
+        });
+      });
+    });
+  });
 }
 
 // ----------------------------------------------------------------------------
@@ -799,33 +794,21 @@ __global__ __launch_bounds__(kBlock) void k_ranks_fq_fwd(
   fq_fwd_block<VEC, NT, CODES, MASK, ACT, kFlatU>(x, y, codes, mask, n, p, blockIdx.x, GateClk{0}, 0u, L);
 }
 
-template <int ACT>
-void launch_ranks_fq_act(bool vec, bool nt, const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n,
-                         const double *gathered, int world, double *st, float *run, double *qp, int sym,
-                         double qden, double eps, float lo, float hi, const SiluLay &L, hipStream_t s) {
+void launch_ranks_fq(int act, bool vec, bool nt, const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n,
+                     const double *gathered, int world, double *st, float *run, double *qp, int sym, double qden,
+                     double eps, float lo, float hi, hipStream_t s) {
+  const SiluLay L = act_lay(act, n);
   const dim3 grid((unsigned)oneshot_grid(cdiv(n, 4)));
-#define K1R(V, T, C, M)                                                                                    \
-  hipLaunchKernelGGL((k_ranks_fq_fwd<V, T, C, M, ACT>), grid, dim3(kBlock), 0, s, x, y, c, m, n, gathered, \
-                     world, st, run, qp, sym, qden, eps, lo, hi, L)
-#define K1RCM(V, T)                             \
-  if (c && m) { K1R(V, T, true, true); }        \
-  else if (c) { K1R(V, T, true, false); }       \
-  else if (m) { K1R(V, T, false, true); }       \
-  else { K1R(V, T, false, false); }
-  if (vec && nt) { K1RCM(true, true) }
-  else if (vec) { K1RCM(true, false) }
-  else { K1RCM(false, false) }
-#undef K1RCM
-#undef K1R
-}
-
-template <int ACT>
-void launch_observe_fq_small_act(bool vec, bool nt, const float *x, float *y, uint8_t *c, uint64_t *m, int64_t n,
-                                 double *st, float *run, double *qp, int sym, double qden, double eps, float lo,
-                                 float hi, const SiluLay &L, hipStream_t s) {
-  if (vec && nt) launch_observe_fq_small<true, true, ACT>(x, y, c, m, n, st, run, qp, sym, qden, eps, lo, hi, L, s);
-  else if (vec) launch_observe_fq_small<true, false, ACT>(x, y, c, m, n, st, run, qp, sym, qden, eps, lo, hi, L, s);
-  else launch_observe_fq_small<false, false, ACT>(x, y, c, m, n, st, run, qp, sym, qden, eps, lo, hi, L, s);
+  with_act(act, [&](auto A) {
+    with_vec_nt(vec, nt, [&](auto V, auto N) {
+      with_bool2(c != nullptr, m != nullptr, [&](auto C, auto M) {
+        hipLaunchKernelGGL((k_ranks_fq_fwd<decltype(V)::value, decltype(N)::value, decltype(C)::value,
+                                           decltype(M)::value, decltype(A)::value>),
+                           grid, dim3(kBlock), 0, s, x, y, c, m, n, gathered, world, st, run, qp, sym, qden, eps, lo,
+                           hi, L);
+      });
+    });
+  });
 }
 
 // ----------------------------------------------------------------------------
@@ -1028,22 +1011,6 @@ __global__ __launch_bounds__(kBlock) void k_selftest_fq(int mode, const float *_
   }
 }
 
-template <int ACT, bool VEC, bool NT, int G>
-void launch_observe_g(const float *x, int64_t n, double *stats_out, float *run_minmax, double *qp_out,
-                      int sym, double qden, double eps, double *ws, uint32_t *counter, int64_t grid,
-                      const SiluLay &L, hipStream_t st) {
-  hipLaunchKernelGGL((k_observe<VEC, NT, ACT, G>), dim3((unsigned)grid), dim3(kBlock), 0, st, x, n,
-                     stats_out, run_minmax, qp_out, sym, qden, eps, ws, counter, L);
-}
-
-template <int ACT, bool VEC, bool NT>
-void launch_observe_loop(const float *x, int64_t n, double *stats_out, float *run_minmax, double *qp_out,
-                         int sym, double qden, double eps, double *ws, uint32_t *counter, int64_t grid,
-                         const SiluLay &L, hipStream_t st) {
-  hipLaunchKernelGGL((k_observe_loop<VEC, NT, ACT, kObsU>), dim3((unsigned)grid), dim3(kBlock), 0, st, x,
-                     n, stats_out, run_minmax, qp_out, sym, qden, eps, ws, counter, L);
-}
-
 // K2 grid: grid-stride kernel (default) or the one-shot kernel (VSIQ_TUNE_OBS_KERNEL 1)
 // Tensors of at most kObsSingle groups (8K elements: one load round per lane) take ONE
 // workgroup and skip the record / arrival / fold chain.  (At 64K elements a single
@@ -1065,32 +1032,26 @@ inline int64_t observe_grid(int64_t ng) {
   return std::min<int64_t>(kObsGrid, std::max<int64_t>(1, cdiv(ng, (int64_t)kBlock * kObsU)));
 }
 
-template <int ACT>
-void launch_observe(bool vec, bool nt, const float *x, int64_t n, double *stats_out, float *run_minmax,
-                    double *qp_out, int sym, double qden, double eps, double *ws, uint32_t *counter,
-                    const SiluLay &L, hipStream_t st) {
+void launch_observe(int act, bool vec, bool nt, const float *x, int64_t n, double *stats_out, float *run_minmax,
+                    double *qp_out, int sym, double qden, double eps, double *ws, uint32_t *counter, hipStream_t st) {
+  const SiluLay L = act_lay(act, n);
   const int64_t ng = cdiv(n, 4);
-  const int64_t grid = observe_grid(ng);
-  if (g_tune.obs_kernel != 1) {
-    if (vec && nt) launch_observe_loop<ACT, true, true>(x, n, stats_out, run_minmax, qp_out, sym, qden, eps, ws, counter, grid, L, st);
-    else if (vec) launch_observe_loop<ACT, true, false>(x, n, stats_out, run_minmax, qp_out, sym, qden, eps, ws, counter, grid, L, st);
-    else launch_observe_loop<ACT, false, false>(x, n, stats_out, run_minmax, qp_out, sym, qden, eps, ws, counter, grid, L, st);
-    return;
-  }
-  // one-shot: K4's groups-per-lane rule (8 -> 4) and grid
-  const int per_lane = obs_groups_per_lane(ng);
-#define VSIQ_OBS(V, N)                                                                              \
-  (per_lane == kLsqGroups                                                                           \
-       ? launch_observe_g<ACT, V, N, kLsqGroups>(x, n, stats_out, run_minmax, qp_out, sym, qden, eps, \
-                                                 ws, counter, grid, L, st)                          \
-   : per_lane == 4 ? launch_observe_g<ACT, V, N, 4>(x, n, stats_out, run_minmax, qp_out, sym, qden,  \
-                                                    eps, ws, counter, grid, L, st)                  \
-                   : launch_observe_g<ACT, V, N, 2>(x, n, stats_out, run_minmax, qp_out, sym, qden,  \
-                                                    eps, ws, counter, grid, L, st))
-  if (vec && nt) VSIQ_OBS(true, true);
-  else if (vec) VSIQ_OBS(true, false);
-  else VSIQ_OBS(false, false);
-#undef VSIQ_OBS
+  const dim3 grid((unsigned)observe_grid(ng));
+  with_act(act, [&](auto A) {
+    with_vec_nt(vec, nt, [&](auto V, auto N) {
+      if (g_tune.obs_kernel != 1) {
+        hipLaunchKernelGGL((k_observe_loop<decltype(V)::value, decltype(N)::value, decltype(A)::value, kObsU>), grid,
+                           dim3(kBlock), 0, st, x, n, stats_out, run_minmax, qp_out, sym, qden, eps, ws, counter, L);
+        return;
+      }
+      // one-shot: K4's groups-per-lane rule (8 -> 4) and grid
+      with_int<kLsqGroups, 4, 2>(obs_groups_per_lane(ng), [&](auto G) {
+        hipLaunchKernelGGL((k_observe<decltype(V)::value, decltype(N)::value, decltype(A)::value, decltype(G)::value>),
+                           grid, dim3(kBlock), 0, st, x, n, stats_out, run_minmax, qp_out, sym, qden, eps, ws, counter,
+                           L);
+      });
+    });
+  });
 }
 
 int observe(const float *x, int64_t n, int act, double *stats_out, float *run_minmax, double *qp_out,
@@ -1103,8 +1064,8 @@ int observe(const float *x, int64_t n, int act, double *stats_out, float *run_mi
   if (ws_len < fold_records(grid) * kPartials) return VSIQ_E_WS;
   // kObsTemporalMB: observe + quantize (K2 -> K1) may re-read x from the Infinity Cache
   const bool nt = g_tune.nontemporal != 0 && !((n * 4) >> 20 < kObsTemporalMB);
-  VSIQ_ACT(act, launch_observe, vec, nt, x, n, stats_out, run_minmax, qp_out,
-           symmetric, qden, eps, ws, counter, act_lay(act, n), (hipStream_t)stream);
+  launch_observe(act, vec, nt, x, n, stats_out, run_minmax, qp_out, symmetric, qden, eps, ws, counter,
+                 (hipStream_t)stream);
   return launch_rc();
 }
 
@@ -1126,24 +1087,14 @@ inline int64_t observe_part_grid(int64_t n) {
   return std::min<int64_t>(cap, std::max<int64_t>(1, cdiv(units, u)));
 }
 
-template <int ACT, int U>
-void launch_observe_part_u(bool vec, bool nt, const float *x, int64_t n, double *parts, int64_t grid,
-                           const SiluLay &L, hipStream_t st) {
-  if (vec && nt)
-    hipLaunchKernelGGL((k_observe_part<true, true, ACT, U>), dim3((unsigned)grid), dim3(kBlock), 0, st, x, n, parts, L);
-  else if (vec)
-    hipLaunchKernelGGL((k_observe_part<true, false, ACT, U>), dim3((unsigned)grid), dim3(kBlock), 0, st, x, n, parts, L);
-  else
-    hipLaunchKernelGGL((k_observe_part<false, false, ACT, U>), dim3((unsigned)grid), dim3(kBlock), 0, st, x, n, parts, L);
-}
-
-template <int ACT>
-void launch_observe_part(bool vec, bool nt, const float *x, int64_t n, double *parts, int64_t grid,
-                         const SiluLay &L, hipStream_t st) {
-  const int u = observe_part_u(n);
-  if (u == 8) launch_observe_part_u<ACT, 8>(vec, nt, x, n, parts, grid, L, st);
-  else if (u == 4) launch_observe_part_u<ACT, 4>(vec, nt, x, n, parts, grid, L, st);
-  else launch_observe_part_u<ACT, 2>(vec, nt, x, n, parts, grid, L, st);
+void launch_observe_part(int act, bool vec, bool nt, const float *x, int64_t n, double *parts, int64_t grid,
+                         hipStream_t st) {
+  const SiluLay L = act_lay(act, n);
+  with_act(act, [&](auto A) {
+    with_int<8, 4, 2>(observe_part_u(n), [&](auto U) {
+      launch_observe_part_u<decltype(A)::value, decltype(U)::value>(vec, nt, x, n, parts, grid, L, st);
+    });
+  });
 }
 
 // CU count of the current device (cached; 256 on MI355X)
@@ -1210,35 +1161,19 @@ inline int64_t k2o_records(int64_t n) {
   return cdiv(cdiv(n, 4), (int64_t)k2o_block() * k2o_groups());
 }
 
-template <bool VEC, bool NT, int ACT, int BS>
-void launch_k2o1_bs(int g, int64_t grid, const float *c, float *y, int64_t n, double *parts, const SiluLay &L,
-                    hipStream_t st) {
-#define K2O1(G_) hipLaunchKernelGGL((k_observe_part_out1<VEC, NT, ACT, G_, BS>), dim3((unsigned)grid), dim3(BS), 0, \
-                                    st, c, y, n, parts, L, 0u)
-  switch (g) {
-    case 1: K2O1(1); break;
-    case 2: K2O1(2); break;
-    case 4: K2O1(4); break;
-    case 8: K2O1(8); break;
-    default: K2O1(16); break;
-  }
-#undef K2O1
-}
-
-template <bool VEC, bool NT, int ACT>
-void launch_k2o1(int g, int bs, int64_t grid, const float *c, float *y, int64_t n, double *parts, const SiluLay &L,
-                 hipStream_t st) {
-  if (bs == 1024) launch_k2o1_bs<VEC, NT, ACT, 1024>(g, grid, c, y, n, parts, L, st);
-  else if (bs == 512) launch_k2o1_bs<VEC, NT, ACT, 512>(g, grid, c, y, n, parts, L, st);
-  else launch_k2o1_bs<VEC, NT, ACT, 256>(g, grid, c, y, n, parts, L, st);
-}
-
-template <int ACT>
-void launch_k2o1_act(bool vec, bool nt, int g, int bs, int64_t grid, const float *c, float *y, int64_t n,
-                     double *parts, const SiluLay &L, hipStream_t st) {
-  if (vec && nt) launch_k2o1<true, true, ACT>(g, bs, grid, c, y, n, parts, L, st);
-  else if (vec) launch_k2o1<true, false, ACT>(g, bs, grid, c, y, n, parts, L, st);
-  else launch_k2o1<false, false, ACT>(g, bs, grid, c, y, n, parts, L, st);
+void launch_k2o1(int act, bool vec, bool nt, int g, int bs, int64_t grid, const float *c, float *y, int64_t n,
+                 double *parts, const SiluLay &L, hipStream_t st) {
+  with_act(act, [&](auto A) {
+    with_vec_nt(vec, nt, [&](auto V, auto N) {
+      with_int<1024, 512, 256>(bs, [&](auto BS) {
+        with_int<1, 2, 4, 8, 16>(g, [&](auto G) {
+          hipLaunchKernelGGL((k_observe_part_out1<decltype(V)::value, decltype(N)::value, decltype(A)::value,
+                                                  decltype(G)::value, decltype(BS)::value>),
+                             dim3((unsigned)grid), dim3(decltype(BS)::value), 0, st, c, y, n, parts, L, 0u);
+        });
+      });
+    });
+  });
 }
 
 // K2o's one-round forms (round 5): where 9 groups per lane of 256 lanes make a grid of
@@ -1266,20 +1201,18 @@ bool launch_k2o_gated_g(const float *c, float *y, int64_t n, double *parts, cons
   return true;
 }
 
-template <int ACT, bool VEC, bool NT>
-bool launch_k2o_gated_vn(const float *c, float *y, int64_t n, double *parts, const SiluLay &L, hipStream_t st) {
-  static_assert(kK2oGroups == 2 && kK2oBlock == 256, "the G = 2 gated form is the default grid");
-  // (a 16-groups form is not one round at 26M: 5 workgroups per CU by its registers)
-  return launch_k2o_gated_g<ACT, VEC, NT, 2>(c, y, n, parts, L, st) ||
-         launch_k2o_gated_g<ACT, VEC, NT, 9>(c, y, n, parts, L, st);
-}
-
-template <int ACT>
-bool launch_k2o_gated(bool vec, bool nt, const float *c, float *y, int64_t n, double *parts, const SiluLay &L,
+bool launch_k2o_gated(int act, bool vec, bool nt, const float *c, float *y, int64_t n, double *parts, const SiluLay &L,
                       hipStream_t st) {
-  if (vec && nt) return launch_k2o_gated_vn<ACT, true, true>(c, y, n, parts, L, st);
-  if (vec) return launch_k2o_gated_vn<ACT, true, false>(c, y, n, parts, L, st);
-  return launch_k2o_gated_vn<ACT, false, false>(c, y, n, parts, L, st);
+  static_assert(kK2oGroups == 2 && kK2oBlock == 256, "the G = 2 gated form is the default grid");
+  return with_act(act, [&](auto A) {
+    return with_vec_nt(vec, nt, [&](auto V, auto N) {
+      constexpr int kA = decltype(A)::value;
+      constexpr bool kV = decltype(V)::value, kN = decltype(N)::value;
+      // (a 16-groups form is not one round at 26M: 5 workgroups per CU by its registers)
+      return launch_k2o_gated_g<kA, kV, kN, 2>(c, y, n, parts, L, st) ||
+             launch_k2o_gated_g<kA, kV, kN, 9>(c, y, n, parts, L, st);
+    });
+  });
 }
 
 extern "C" {
@@ -1401,8 +1334,7 @@ int vsiq_act_observe_part_f32(const float *c, int64_t n, int act, double *parts,
   const int64_t grid = observe_part_grid(n);
   if (parts_len < grid * kWaves * VSIQ_PART_LEN) return VSIQ_E_WS;
   const bool vec = aligned16(c) && n % 4 == 0;
-  VSIQ_ACT(act, launch_observe_part, vec, g_tune.nontemporal != 0, c, n, parts, grid, act_lay(act, n),
-           (hipStream_t)stream);
+  launch_observe_part(act, vec, g_tune.nontemporal != 0, c, n, parts, grid, (hipStream_t)stream);
   return launch_rc();
 }
 
@@ -1423,31 +1355,22 @@ int vsiq_act_observe_part_out_f32(const float *c, float *y, int64_t n, int act, 
     if (grid > 0x7fffffffLL) return VSIQ_E_ARG;
     if (parts_len < grid * VSIQ_PART_LEN) return VSIQ_E_WS;
     // default shape knobs: the one-round gated form where the size allows it
-    if (g_tune.k2o_groups == 0 && g_tune.k2o_block == 0 &&
-        VSIQ_ACT(act, launch_k2o_gated, vec, nt, c, y, n, parts, L, st))
+    if (g_tune.k2o_groups == 0 && g_tune.k2o_block == 0 && launch_k2o_gated(act, vec, nt, c, y, n, parts, L, st))
       return launch_rc();
-    VSIQ_ACT(act, launch_k2o1_act, vec, nt, k2o_groups(), k2o_block(), grid, c, y, n, parts, L, st);
+    launch_k2o1(act, vec, nt, k2o_groups(), k2o_block(), grid, c, y, n, parts, L, st);
     return launch_rc();
   }
   const int64_t grid = observe_part_grid(n);
   if (parts_len < grid * kWaves * VSIQ_PART_LEN) return VSIQ_E_WS;
-  const int u = observe_part_u(n);
-#define K2O(A, U_)                                                                                              \
-  if (vec && nt) hipLaunchKernelGGL((k_observe_part_out<true, true, A, U_>), dim3((unsigned)grid), dim3(kBlock), 0, \
-                                    st, c, y, n, parts, L);                                                     \
-  else if (vec) hipLaunchKernelGGL((k_observe_part_out<true, false, A, U_>), dim3((unsigned)grid), dim3(kBlock), 0, \
-                                   st, c, y, n, parts, L);                                                      \
-  else hipLaunchKernelGGL((k_observe_part_out<false, false, A, U_>), dim3((unsigned)grid), dim3(kBlock), 0, st, c,  \
-                          y, n, parts, L);
-#define K2OU(A)                     \
-  if (u == 8) { K2O(A, 8) }         \
-  else if (u == 4) { K2O(A, 4) }    \
-  else { K2O(A, 2) }
-  if (act_kind(act) == kActRelu) { K2OU(kActRelu) }
-  else if (act_kind(act) == kActSilu) { K2OU(kActSilu) }
-  else { K2OU(kActNone) }
-#undef K2OU
-#undef K2O
+  with_act(act, [&](auto A) {
+    with_int<8, 4, 2>(observe_part_u(n), [&](auto U) {
+      with_vec_nt(vec, nt, [&](auto V, auto N) {
+        hipLaunchKernelGGL((k_observe_part_out<decltype(V)::value, decltype(N)::value, decltype(A)::value,
+                                               decltype(U)::value>),
+                           dim3((unsigned)grid), dim3(kBlock), 0, st, c, y, n, parts, L);
+      });
+    });
+  });
   return launch_rc();
 }
 
@@ -1480,15 +1403,12 @@ int vsiq_act_observe_part_multi_f32(const vsiq_part_tensor *tensors, int count, 
     const hipStream_t st = (hipStream_t)stream;
     bool allvec = true;
     for (int k = 0; k < b.count; ++k) allvec = allvec && b.t[k].vec;
-#define K2M(A)                                                                                                 \
-  if (nt && allvec) hipLaunchKernelGGL((k_observe_part_multi<true, A, true>), dim3(blk), dim3(kBlock), 0, st, b); \
-  else if (nt) hipLaunchKernelGGL((k_observe_part_multi<true, A, false>), dim3(blk), dim3(kBlock), 0, st, b);    \
-  else if (allvec) hipLaunchKernelGGL((k_observe_part_multi<false, A, true>), dim3(blk), dim3(kBlock), 0, st, b); \
-  else hipLaunchKernelGGL((k_observe_part_multi<false, A, false>), dim3(blk), dim3(kBlock), 0, st, b);
-    if (act_kind(act) == kActRelu) { K2M(kActRelu) }
-    else if (act_kind(act) == kActSilu) { K2M(kActSilu) }
-    else { K2M(kActNone) }
-#undef K2M
+    with_act(act, [&](auto A) {
+      with_bool2(nt, allvec, [&](auto N, auto AV) {
+        hipLaunchKernelGGL((k_observe_part_multi<decltype(N)::value, decltype(A)::value, decltype(AV)::value>),
+                           dim3(blk), dim3(kBlock), 0, st, b);
+      });
+    });
     const int rc = launch_rc();
     if (rc) return rc;
   }
@@ -1508,9 +1428,8 @@ int vsiq_act_observe_fq_parts_f32(const float *c, float *y, void *codes, uint64_
   if (ws_len < fold_fq_part_grid(n) * kWaves * VSIQ_PART_LEN) return VSIQ_E_WS;
   if (mask && !aligned8(mask)) return VSIQ_E_ALIGN;
   const bool vec = n % 4 == 0 && aligned16(c) && aligned16(y) && (!codes || aligned4(codes));
-  VSIQ_ACT(act, launch_fold_fq_act, vec, g_tune.nontemporal != 0, c, y, (uint8_t *)codes, mask, n, ws,
-           stats_out, run_minmax, qp_out, symmetric, qden, eps, (float)qmin, (float)qmax, act_lay(act, n),
-           (hipStream_t)stream);
+  launch_fold_fq(act, vec, g_tune.nontemporal != 0, c, y, (uint8_t *)codes, mask, n, ws, stats_out, run_minmax,
+                 qp_out, symmetric, qden, eps, (float)qmin, (float)qmax, (hipStream_t)stream);
   return launch_rc();
 }
 
@@ -1524,9 +1443,8 @@ int vsiq_act_observe_fq_grid_f32(const float *c, float *y, void *codes, uint64_t
   if (mask && !aligned8(mask)) return VSIQ_E_ALIGN;
   if (!aligned4(counter)) return VSIQ_E_ALIGN;
   const bool vec = n % 4 == 0 && aligned16(c) && aligned16(y) && (!codes || aligned4(codes));
-  VSIQ_ACT(act, launch_observe_fq_grid_act, vec, g_tune.nontemporal != 0, c, y, (uint8_t *)codes, mask, n, ws,
-           counter, stats_out, run_minmax, qp_out, symmetric, qden, eps, (float)qmin, (float)qmax,
-           act_lay(act, n), (hipStream_t)stream);
+  launch_observe_fq_grid(act, vec, g_tune.nontemporal != 0, c, y, (uint8_t *)codes, mask, n, ws, counter, stats_out,
+                         run_minmax, qp_out, symmetric, qden, eps, (float)qmin, (float)qmax, (hipStream_t)stream);
   return launch_rc();
 }
 
@@ -1538,9 +1456,8 @@ int vsiq_act_fq_fwd_ranks_f32(const float *c, float *y, void *codes, uint64_t *m
   if (oneshot_grid(cdiv(n, 4)) > 0x7fffffffLL) return VSIQ_E_ARG;
   if (mask && !aligned8(mask)) return VSIQ_E_ALIGN;
   const bool vec = n % 4 == 0 && aligned16(c) && aligned16(y) && (!codes || aligned4(codes));
-  VSIQ_ACT(act, launch_ranks_fq_act, vec, g_tune.nontemporal != 0, c, y, (uint8_t *)codes, mask, n, gathered,
-           world, stats_out, run_minmax, qp_out, symmetric, qden, eps, (float)qmin, (float)qmax, act_lay(act, n),
-           (hipStream_t)stream);
+  launch_ranks_fq(act, vec, g_tune.nontemporal != 0, c, y, (uint8_t *)codes, mask, n, gathered, world, stats_out,
+                  run_minmax, qp_out, symmetric, qden, eps, (float)qmin, (float)qmax, (hipStream_t)stream);
   return launch_rc();
 }
 
@@ -1551,9 +1468,8 @@ int vsiq_act_observe_fq_f32(const float *c, float *y, void *codes, uint64_t *mas
     return VSIQ_E_ARG;
   if (mask && !aligned8(mask)) return VSIQ_E_ALIGN;
   const bool vec = n % 4 == 0 && aligned16(c) && aligned16(y) && (!codes || aligned4(codes));
-  VSIQ_ACT(act, launch_observe_fq_small_act, vec, g_tune.nontemporal != 0, c, y, (uint8_t *)codes, mask, n,
-           stats_out, run_minmax, qp_out, symmetric, qden, eps, (float)qmin, (float)qmax, act_lay(act, n),
-           (hipStream_t)stream);
+  launch_observe_fq_small(act, vec, g_tune.nontemporal != 0, c, y, (uint8_t *)codes, mask, n, stats_out, run_minmax,
+                          qp_out, symmetric, qden, eps, (float)qmin, (float)qmax, (hipStream_t)stream);
   return launch_rc();
 }
 

@@ -1,5 +1,6 @@
 // k_fq.hip — K1 per-tensor fake-quant forward (optionally behind a fused ReLU/SiLU,
 // K5), and its C ABI entry points.
+#include "dispatch.cuh"
 #include "k_body.cuh"
 
 namespace vsiq {
@@ -47,23 +48,6 @@ void launch_fq_k(const float *x, float *y, uint8_t *codes, uint64_t *mask, int64
   store_gate_launched(gs, st);   // for the 9-group site: a tuning sample of "no gate" times the kFlatU grid
 }
 
-template <int ACT, bool VEC, bool NT>
-void launch_fq_act(const float *x, float *y, uint8_t *codes, uint64_t *mask, int64_t n,
-                   const QPSrc &src, const SiluLay &L, hipStream_t st) {
-  if (codes && mask) launch_fq_k<VEC, NT, true, true, ACT>(x, y, codes, mask, n, src, L, st);
-  else if (codes) launch_fq_k<VEC, NT, true, false, ACT>(x, y, codes, mask, n, src, L, st);
-  else if (mask) launch_fq_k<VEC, NT, false, true, ACT>(x, y, codes, mask, n, src, L, st);
-  else launch_fq_k<VEC, NT, false, false, ACT>(x, y, codes, mask, n, src, L, st);
-}
-
-template <int ACT>
-void launch_fq(bool vec, bool nt, const float *x, float *y, uint8_t *codes, uint64_t *mask, int64_t n,
-               const QPSrc &src, const SiluLay &L, hipStream_t st) {
-  if (vec && nt) launch_fq_act<ACT, true, true>(x, y, codes, mask, n, src, L, st);
-  else if (vec) launch_fq_act<ACT, true, false>(x, y, codes, mask, n, src, L, st);
-  else if (nt) launch_fq_act<ACT, false, true>(x, y, codes, mask, n, src, L, st);
-  else launch_fq_act<ACT, false, false>(x, y, codes, mask, n, src, L, st);
-}
 
 int fq_fwd(const float *x, float *y, void *codes, uint64_t *mask, int64_t n, int act,
            const double *qp_dev, const double *scale_dev, double scale_host, const double *zp_dev,
@@ -78,7 +62,15 @@ int fq_fwd(const float *x, float *y, void *codes, uint64_t *mask, int64_t n, int
   const bool vec = (n % 4 == 0) && aligned16(x) && aligned16(y) && (!codes || aligned4(codes));
   const bool nt = g_tune.nontemporal != 0;
   uint8_t *c = (uint8_t *)codes;
-  VSIQ_ACT(act, launch_fq, vec, nt, x, y, c, mask, n, src, act_lay(act, n), st);
+  const SiluLay L = act_lay(act, n);
+  with_act(act, [&](auto A) {   // all four (VEC, NT) pairs: the scalar path is non-temporal too
+    with_vec_nt4(vec, nt, [&](auto V, auto N) {
+      with_bool2(c != nullptr, mask != nullptr, [&](auto C, auto M) {
+        launch_fq_k<decltype(V)::value, decltype(N)::value, decltype(C)::value, decltype(M)::value,
+                    decltype(A)::value>(x, y, c, mask, n, src, L, st);
+      });
+    });
+  });
   return launch_rc();
 }
 

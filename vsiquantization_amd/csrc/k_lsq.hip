@@ -1,5 +1,6 @@
 // k_lsq.hip — K4 learnable (LSQ) backward: grad_x + f64 scale / zero-point gradient
 // sums (optionally through a fused ReLU/SiLU, K5), and its C ABI entry points.
+#include "dispatch.cuh"
 #include "k_body.cuh"
 
 namespace vsiq {
@@ -110,29 +111,19 @@ inline int lsq_part_groups_per_lane(int64_t n) {
   return g > 0 ? g : (n >= ((int64_t)48 << 20) ? 4 : 2);
 }
 
-template <int ACT, bool VEC, bool NT>
-void launch_lsq_act(const float *g, const float *x, float *gx, int64_t n, const QPSrc &src, int zpl,
-                    double gscale, double *grad_out, double *ws, uint32_t *counter, int64_t grid,
-                    const SiluLay &L, hipStream_t st) {
+// all four (VEC, NT) pairs: the scalar path streams its loads and stores non-temporally too
+void launch_lsq(int act, bool vec, bool nt, const float *g, const float *x, float *gx, int64_t n, const QPSrc &src,
+                int zpl, double gscale, double *grad_out, double *ws, uint32_t *counter, int64_t grid, hipStream_t st) {
+  const SiluLay L = act_lay(act, n);
   const int per_lane = counter ? lsq_groups_per_lane(cdiv(n, 4)) : lsq_part_groups_per_lane(n);
-  if (per_lane == kLsqGroups)
-    launch_lsq_g<ACT, VEC, NT, kLsqGroups>(g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
-  else if (per_lane == 8)
-    launch_lsq_g<ACT, VEC, NT, 8>(g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
-  else if (per_lane == 4)
-    launch_lsq_g<ACT, VEC, NT, 4>(g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
-  else
-    launch_lsq_g<ACT, VEC, NT, 2>(g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
-}
-
-template <int ACT>
-void launch_lsq(bool vec, bool nt, const float *g, const float *x, float *gx, int64_t n,
-                const QPSrc &src, int zpl, double gscale, double *grad_out, double *ws,
-                uint32_t *counter, int64_t grid, const SiluLay &L, hipStream_t st) {
-  if (vec && nt) launch_lsq_act<ACT, true, true>(g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
-  else if (vec) launch_lsq_act<ACT, true, false>(g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
-  else if (nt) launch_lsq_act<ACT, false, true>(g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
-  else launch_lsq_act<ACT, false, false>(g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
+  with_act(act, [&](auto A) {
+    with_vec_nt4(vec, nt, [&](auto V, auto N) {
+      with_int<kLsqGroups, 8, 4, 2>(per_lane, [&](auto G) {
+        launch_lsq_g<decltype(A)::value, decltype(V)::value, decltype(N)::value, decltype(G)::value>(
+            g, x, gx, n, src, zpl, gscale, grad_out, ws, counter, grid, L, st);
+      });
+    });
+  });
 }
 
 int lsq_bwd(const float *g, const float *x, float *gx, int64_t n, int act, const double *scale_dev,
@@ -149,8 +140,7 @@ int lsq_bwd(const float *g, const float *x, float *gx, int64_t n, int act, const
   if (zp_learn < 0 || zp_learn > 2) return VSIQ_E_ARG;
   QPSrc src{nullptr, scale_dev, zp_dev, scale_host, zp_host, (float)qmin, (float)qmax, zp_learn == 1, 0};
   const bool nt = g_tune.nontemporal != 0;
-  VSIQ_ACT(act, launch_lsq, vec, nt, g, x, gx, n, src, zp_learn != 0, gscale, grad_out, ws, counter, grid,
-           act_lay(act, n), (hipStream_t)stream);
+  launch_lsq(act, vec, nt, g, x, gx, n, src, zp_learn != 0, gscale, grad_out, ws, counter, grid, (hipStream_t)stream);
   return launch_rc();
 }
 
@@ -167,8 +157,7 @@ int lsq_bwd_part(const float *g, const float *x, float *gx, int64_t n, int act, 
   if (zp_learn < 0 || zp_learn > 1) return VSIQ_E_ARG;   // the deferred fold knows modes 0 / 1 only
   QPSrc src{nullptr, scale_dev, zp_dev, scale_host, zp_host, (float)qmin, (float)qmax, zp_learn, 0};
   const bool nt = g_tune.nontemporal != 0;
-  VSIQ_ACT(act, launch_lsq, vec, nt, g, x, gx, n, src, zp_learn, 0.0, nullptr, records, nullptr, grid,
-           act_lay(act, n), (hipStream_t)stream);
+  launch_lsq(act, vec, nt, g, x, gx, n, src, zp_learn, 0.0, nullptr, records, nullptr, grid, (hipStream_t)stream);
   return launch_rc();
 }
 
@@ -488,15 +477,12 @@ void launch_pcr_lsq(const float *g, const float *x, float *gx, int64_t rows, int
                     const double *scale, const double *zp, int zp_learn, float lo, float hi,
                     double gscale, double *gs, double *gz, hipStream_t st) {
   const int64_t per_lane = cdiv(cdiv(rowlen, 4), (int64_t)kBlock);
-#define VSIQ_PCR(ZPL)                                                                               \
-  (per_lane <= 1   ? launch_pcr_nv<VEC, NT, ZPL, 1>(g, x, gx, rows, rowlen, scale, zp, lo, hi, gscale, gs, gz, st) \
-   : per_lane <= 2 ? launch_pcr_nv<VEC, NT, ZPL, 2>(g, x, gx, rows, rowlen, scale, zp, lo, hi, gscale, gs, gz, st) \
-   : per_lane <= 3 ? launch_pcr_nv<VEC, NT, ZPL, 3>(g, x, gx, rows, rowlen, scale, zp, lo, hi, gscale, gs, gz, st) \
-   : per_lane <= 5 ? launch_pcr_nv<VEC, NT, ZPL, 5>(g, x, gx, rows, rowlen, scale, zp, lo, hi, gscale, gs, gz, st) \
-                   : launch_pcr_nv<VEC, NT, ZPL, 9>(g, x, gx, rows, rowlen, scale, zp, lo, hi, gscale, gs, gz, st))
-  if (zp_learn) VSIQ_PCR(true);
-  else VSIQ_PCR(false);
-#undef VSIQ_PCR
+  with_bool(zp_learn != 0, [&](auto ZPL) {
+    with_int_le<1, 2, 3, 5, 9>(per_lane, [&](auto NV) {
+      launch_pcr_nv<VEC, NT, decltype(ZPL)::value, decltype(NV)::value>(g, x, gx, rows, rowlen, scale, zp, lo, hi,
+                                                                        gscale, gs, gz, st);
+    });
+  });
 }
 
 template <bool VEC, bool NT>
@@ -667,16 +653,10 @@ int64_t launch_pcc_lsq(const float *g, const float *x, float *gx, int64_t rows, 
                        hipStream_t st) {
   const int64_t images = rows / channels, nb = pcc_images(rowlen);
   const int64_t iblocks = cdiv(images, nb), grid = iblocks * channels;
-#define VSIQ_PCC(ZPL, AR) \
-  launch_pcc_k<NT, ZPL, AR>(g, x, gx, images, rowlen, nb, channels, grid, scale, zp, lo, hi, ws, counters, gscale, gs, gz, st)
-  if (counters) {
-    if (zp_learn) VSIQ_PCC(true, true);
-    else VSIQ_PCC(false, true);
-  } else {
-    if (zp_learn) VSIQ_PCC(true, false);
-    else VSIQ_PCC(false, false);
-  }
-#undef VSIQ_PCC
+  with_bool2(zp_learn != 0, counters != nullptr, [&](auto ZPL, auto AR) {
+    launch_pcc_k<NT, decltype(ZPL)::value, decltype(AR)::value>(g, x, gx, images, rowlen, nb, channels, grid, scale, zp,
+                                                                lo, hi, ws, counters, gscale, gs, gz, st);
+  });
   return iblocks * channels;   // record rows for k_pcm_lsq_fold (one chunk each)
 }
 

@@ -27,6 +27,7 @@
 //          loads, kStdU groups in flight per lane), one fold.
 // Both sums (|act(x)| and act(x)) ride the same pass.  HBM: 4 B / element read; the
 // level-1 nodes (8 B per 256 elements at V = 8) are written once and read once.
+#include "dispatch.cuh"
 #include "mean_cascade.cuh"
 
 namespace vsiq {
@@ -323,16 +324,6 @@ void launch_mean(const MeanArgs &a, const MeanLay &m, hipStream_t st) {
   hipLaunchKernelGGL((k_mean_chunks<V, ACT>), dim3((unsigned)m.nchunks), dim3(256), 0, st, a);
 }
 
-template <int ACT>
-void launch_mean8(const MeanArgs &a, const MeanLay &m, hipStream_t st) {
-  launch_mean<8, ACT>(a, m, st);
-}
-
-template <int ACT>
-void launch_mean16(const MeanArgs &a, const MeanLay &m, hipStream_t st) {
-  launch_mean<16, ACT>(a, m, st);
-}
-
 }  // namespace
 
 int64_t mean_ws_bytes(int64_t n, int vec, int threads) {
@@ -372,13 +363,14 @@ int vsiq_torch_mean_f32(const float *x, int64_t n, int act, int vec, int threads
   a.csum = a.l2 + m.nchunks * a.l2_max * 4 * vec;
   a.L = act_lay(act, n);
   if (m.nchunks > 0) {
-    if (vec == 8) VSIQ_ACT(act, launch_mean8, a, m, st);
-    else VSIQ_ACT(act, launch_mean16, a, m, st);
+    with_act(act, [&](auto A) {
+      with_int<8, 16>(vec, [&](auto V) { launch_mean<decltype(V)::value, decltype(A)::value>(a, m, st); });
+    });
   }
   hipLaunchKernelGGL(k_mean_final, dim3(1), dim3(64), 0, st, a.csum, m, vec, threads, n, out4, stats);
   if (stats) {
     double *part = reinterpret_cast<double *>(a.csum + (m.nchunks > 0 ? m.nchunks : 1));
-    VSIQ_ACT(act, launch_std, x, n, stats, a.L, part, st);
+    with_act(act, [&](auto A) { launch_std<decltype(A)::value>(x, n, stats, a.L, part, st); });
     hipLaunchKernelGGL(k_std_final, dim3(1), dim3(256), 0, st, part, n, stats);
   }
   return launch_rc();

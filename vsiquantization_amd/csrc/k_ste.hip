@@ -1,5 +1,5 @@
 // k_ste.hip — straight-through backward from the saved 1-bit mask, and its C ABI.
-#include "vsiq_common.cuh"
+#include "dispatch.cuh"
 
 namespace vsiq {
 
@@ -106,14 +106,6 @@ void launch_ste_act(const float *g, const uint64_t *m, const float *pre, float *
   store_gate_launched(gs, st);
 }
 
-template <int ACT>
-void launch_ste(bool vec, bool nt, const float *g, const uint64_t *m, const float *pre, float *gx,
-                int64_t rows, int64_t rowlen, const double *sdev, double shost, const SiluLay &L, hipStream_t st) {
-  if (vec && nt) launch_ste_act<ACT, true, true>(g, m, pre, gx, rows, rowlen, sdev, shost, L, st);
-  else if (vec) launch_ste_act<ACT, true, false>(g, m, pre, gx, rows, rowlen, sdev, shost, L, st);
-  else if (nt) launch_ste_act<ACT, false, true>(g, m, pre, gx, rows, rowlen, sdev, shost, L, st);
-  else launch_ste_act<ACT, false, false>(g, m, pre, gx, rows, rowlen, sdev, shost, L, st);
-}
 
 int ste_bwd(const float *g, const uint64_t *mask, const float *pre, float *gx, int64_t n, int act,
             const double *scale_dev, int64_t rowlen, double scale_host, void *stream) {
@@ -127,8 +119,14 @@ int ste_bwd(const float *g, const uint64_t *mask, const float *pre, float *gx, i
   if (rows * oneshot_grid(cdiv(rowlen, 4)) > 0x7fffffffLL) return VSIQ_E_ARG;
   const bool vec = (rowlen % 4 == 0) && aligned16(g) && aligned16(gx) && (!pre || aligned16(pre));
   const bool nt = g_tune.nontemporal != 0;
-  VSIQ_ACT(act, launch_ste, vec, nt, g, mask, pre, gx, rows, rowlen, scale_dev, scale_host,
-           act_lay(act, n), (hipStream_t)stream);
+  const SiluLay L = act_lay(act, n);
+  with_act(act, [&](auto A) {   // all four (VEC, NT) pairs: the scalar path is non-temporal too
+    with_vec_nt4(vec, nt, [&](auto V, auto N) {
+      launch_ste_act<decltype(A)::value, decltype(V)::value, decltype(N)::value>(g, mask, pre, gx, rows, rowlen,
+                                                                                 scale_dev, scale_host, L,
+                                                                                 (hipStream_t)stream);
+    });
+  });
   return launch_rc();
 }
 

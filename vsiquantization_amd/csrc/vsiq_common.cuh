@@ -561,11 +561,6 @@ inline SiluLay act_lay(int act, int64_t n) {
   return act_kind(act) == kActSilu ? silu_lay(n, act_ref(act)) : SiluLay{};
 }
 
-// runtime act -> template dispatch (on the activation kind)
-#define VSIQ_ACT(ACTV, F, ...)                                                 \
-  (act_kind(ACTV) == kActRelu ? F<kActRelu>(__VA_ARGS__)                       \
-                              : act_kind(ACTV) == kActSilu ? F<kActSilu>(__VA_ARGS__) : F<kActNone>(__VA_ARGS__))
-
 // where qparams come from (one struct, passed by value -> kernarg / SGPRs)
 struct QPSrc {
   const double *qp;     // observer record [scale, zp, ...] or null
@@ -1270,7 +1265,7 @@ inline bool aligned8(const void *p) { return ((uintptr_t)p & 7u) == 0; }
 // when a workgroup holds its stores back for ~2 us after its loads have landed: the
 // device then reads, and then writes, instead of interleaving the two from the first
 // returned load on (C2 size, 1024 workgroups of 256 lanes x 9 groups: STE 14.0 ->
-// 11.9 us, 5.4 -> 6.3 TB/s; measured, tools/exp/phase_*).  Called after a barrier, with
+// 11.9 us, 5.4 -> 6.3 TB/s; measured).  Called after a barrier, with
 // a wave-uniform unit count (512 clocks each); a pure delay, never a correctness issue.
 __device__ __forceinline__ void defer_stores(uint32_t units) {
   for (uint32_t k = 0; k < units; ++k) __builtin_amdgcn_s_sleep(8);
@@ -1304,7 +1299,7 @@ __device__ __forceinline__ void gate_pass(uint32_t gate, const GateClk &c) {
 // workgroups per CU and all of them resident at once (`occ` per CU); grids under 2
 // workgroups per CU gain nothing and grids of more than one round lose (the next round
 // waits behind the gate).  The gate's optimum is sharp and moves with the box's HBM:
-// K3 at C2 on one MI355X (tools/exp/gate_timeline.py) 4.52 / 5.00 / 5.28 / 5.60 /
+// K3 at C2 on one MI355X 4.52 / 5.00 / 5.28 / 5.60 /
 // 6.03 us -> 12.8 / 12.2 / 12.4 / 12.7 / 13.1 us per launch (15.2 without a gate), and
 // the fixed 1.05 x (read bytes at 7.5 TB/s) of round 1 sat at the no-gate time on
 // another box.  So the gate is tuned online per (kernel, grid, bytes, device): the
@@ -1367,7 +1362,7 @@ inline int64_t oneshot_grid(int64_t groups) {
 // K4 groups per lane: 4.  Since the two-level fold (fold_arrivals) a workgroup's
 // epilogue no longer serializes on one counter, and 4 groups per lane stream better
 // than 16 (16-deep straight-line code) at every size measured on MI355X
-// (tools/exp/k4_sizes.py, fused ReLU: 105M elements 230 -> 216 us, 3.3M 19.1 -> 15.4,
+// (fused ReLU: 105M elements 230 -> 216 us, 3.3M 19.1 -> 15.4,
 // 296K 16.4 -> 7.3); 2 per lane pays the epilogue twice as often (105M: 342 us).
 // Override: VSIQ_TUNE_LSQ_GROUPS (2 / 4 / 16).
 // From 20M elements on, 8 per lane: half the workgroups, half the arrivals

@@ -423,7 +423,7 @@ def observe_tensor(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, eps: 
 
 # K8 (one workgroup holds the tensor) up to here; K9 above: through the API K8 is
 # 10.9-12.1 us against 17.9-18.2 us for K2 + K1 at 432-16384 elements, but its GPU time
-# grows past K2 + K1's ~9 us above ~16K elements (65536: 16.2 us; tools/exp/k8_bench.py).
+# grows past K2 + K1's ~9 us above ~16K elements (65536: 16.2 us).
 _K8_ELEMS = 16384
 
 
