@@ -41,11 +41,14 @@ FLAGS = [
 ]
 
 
-# per-source extra flags.  k_flat.hip (K2 / K2p / K2m observers): without SLP
+# per-source extra flags.  k_observe.hip (K2 / K2p / K2m observers): without SLP
 # vectorization the observer's |x| sums stay scalar adds with free abs modifiers instead
 # of v_pk_add_f32 fed by v_and / v_mov pairs -- C5's K2m 175 -> 168 us on MI355X (C2 / C3
-# / C4 kernels measured unchanged with it, so they keep the default)
-FILE_FLAGS = {"k_flat.hip": ["-fno-slp-vectorize"]}
+# / C4 kernels measured unchanged with it, so they keep the default).  k_observe_fq.hip
+# and k_lib.hip were one translation unit with it: their kernels keep the flag they were
+# built with.
+_NO_SLP = ["-fno-slp-vectorize"]
+FILE_FLAGS = {"k_observe.hip": _NO_SLP, "k_observe_fq.hip": _NO_SLP, "k_lib.hip": _NO_SLP}
 
 
 def hipcc() -> str:

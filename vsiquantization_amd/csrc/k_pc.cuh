@@ -86,15 +86,9 @@ __device__ __forceinline__ QP pc_row_qparams(float mn, float mx, uint32_t nan, R
       a.row_stats[row * 3 + 2] = s2;
     }
   }
-  QP p;
-  p.s = (float)s;
-  p.z = (float)z;
-  p.lo = a.lo;
-  p.hi = a.hi;
-  p.discrete = 0;
-  p.d = make_fastdiv(p.s);
-  p.fast = (fq_fast_qp(p.s, p.z) && !nan &&
-            __builtin_fmaxf(__builtin_fabsf(mn), __builtin_fabsf(mx)) <= 0x1p62f) ? 1u : 0u;
+  QP p = make_qp((float)s, (float)z, a.lo, a.hi, 0);
+  // the fast path also needs the whole row finite and in range (QP::fast)
+  p.fast = (p.fast && !nan && __builtin_fmaxf(__builtin_fabsf(mn), __builtin_fabsf(mx)) <= 0x1p62f) ? 1u : 0u;
   return p;
 }
 

@@ -224,6 +224,20 @@ __device__ __forceinline__ uint32_t fq_fast_qp(float s, float z) {
   return (s_ok && z_ok) ? 1u : 0u;
 }
 
+// The element arithmetic's parameters from fp32 (scale, zero point): the divisor's
+// reciprocal and whether the no-check fast path applies.
+__device__ __forceinline__ QP make_qp(float s, float z, float lo, float hi, int discrete) {
+  QP p;
+  p.s = s;
+  p.z = z;
+  p.lo = lo;
+  p.hi = hi;
+  p.discrete = discrete;
+  p.d = make_fastdiv(p.s);
+  p.fast = fq_fast_qp(p.s, p.z);
+  return p;
+}
+
 __device__ __forceinline__ float fq_quot(float x, const FastDiv &d) {
   const float q0 = x * d.r;
   const float e0 = __builtin_fmaf(-q0, d.b, x);
@@ -609,15 +623,7 @@ __device__ __forceinline__ QP load_qp(const QPSrc &a) {
       z = zr < (double)a.lo ? (double)a.lo : (zr > (double)a.hi ? (double)a.hi : zr);
     }
   }
-  QP p;
-  p.s = (float)s;
-  p.z = (float)z;
-  p.lo = a.lo;
-  p.hi = a.hi;
-  p.discrete = a.discrete;
-  p.d = make_fastdiv(p.s);
-  p.fast = fq_fast_qp(p.s, p.z);
-  return p;
+  return make_qp((float)s, (float)z, a.lo, a.hi, a.discrete);
 }
 
 // ----------------------------------------------------------------------------
@@ -942,26 +948,6 @@ __device__ __forceinline__ bool arrive_last(uint32_t *counter) {
   return s_last != 0;
 }
 
-// Last-workgroup combine of the per-workgroup partial records: thread t folds
-// records t, t+B, t+2B, ... in that fixed order (deterministic), but the loads of 4
-// consecutive records are issued together -- a serial load->add chain over thousands
-// of records was a multi-microsecond tail on large grids.
-template <int K, typename F>
-__device__ __forceinline__ void fold_partials(const double *ws, int nrec, F &&f) {
-  for (int b0 = threadIdx.x; b0 < nrec; b0 += 4 * kBlock) {
-    double r[4][K];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int b = b0 + u * kBlock < nrec ? b0 + u * kBlock : nrec - 1;
-#pragma unroll
-      for (int k = 0; k < K; ++k) r[u][k] = partial_load(ws + (int64_t)b * kPartials + k);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (b0 + u * kBlock < nrec) f(r[u]);
-  }
-}
-
 // ----------------------------------------------------------------------------
 // Two-level fold of per-workgroup partial records (K doubles each, record b at
 // ws + b * kPartials, stored by thread 0 with partial_store).  Op supplies
@@ -973,6 +959,29 @@ __device__ __forceinline__ void fold_partials(const double *ws, int nrec, F &&f)
 // folds combines those.  Fixed assignment and trees: deterministic for a given grid.
 // The workspace needs nb + kArriveGroups records (vsiq_workspace_doubles).
 // ----------------------------------------------------------------------------
+// Every lane's partial fold `a` -> the workgroup's fold in thread 0: a wave reduction,
+// lane 0 of each wave through `s_w`, thread 0 adds waves 1.. in order.  The tail of
+// every fold over records (fold_block here, k_observe.cuh's).
+template <typename Op>
+__device__ __forceinline__ void fold_waves(double (&a)[Op::K], double (&s_w)[kWaves][Op::K]) {
+  constexpr int K = Op::K;
+  Op::wave(a);
+  if (threadIdx.x % kWave == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) s_w[threadIdx.x / kWave][k] = a[k];
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < kWaves; ++w) {
+      double r[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) r[k] = s_w[w][k];
+      Op::add(a, r);
+    }
+}
+
+// Thread t folds records t, t+B, t+2B, ... in that fixed order (deterministic), but
+// the loads of 4 consecutive records are issued together -- a serial load->add chain
+// over thousands of records was a multi-microsecond tail on large grids.
 template <typename Op>
 __device__ __forceinline__ void fold_block(const double *ws, uint32_t first, uint32_t count, uint32_t stride,
                                            double (&a)[Op::K]) {
@@ -991,18 +1000,7 @@ __device__ __forceinline__ void fold_block(const double *ws, uint32_t first, uin
       if (j0 + u * kBlock < count) Op::add(a, r[u]);
   }
   __shared__ double s_w[kWaves][K];
-  Op::wave(a);
-  if (threadIdx.x % kWave == 0)
-#pragma unroll
-    for (int k = 0; k < K; ++k) s_w[threadIdx.x / kWave][k] = a[k];
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < kWaves; ++w) {
-      double r[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) r[k] = s_w[w][k];
-      Op::add(a, r);
-    }
+  fold_waves<Op>(a, s_w);
   __syncthreads();
 }
 

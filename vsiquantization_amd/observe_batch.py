@@ -1,4 +1,4 @@
-"""Queued deferred observer calls (K2m, csrc/k_flat.hip).
+"""Queued deferred observer calls (K2m, csrc/k_observe.hip).
 
 In deferred calibration (``QuantizationManager.dist_defer``, the default of
 ``calibrate_qat_model``) an observer call only writes partial records that nothing reads
