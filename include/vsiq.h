@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define VSIQ_ABI_VERSION 11
+#define VSIQ_ABI_VERSION 12
 
 /* uint32 words of a reducing kernel's arrival `counter` (all 0 before the first call) */
 #define VSIQ_COUNTER_WORDS 64
@@ -541,6 +541,49 @@ int vsiq_act_lsq_bwd_f32(const float *g, const float *c, float *gc, int64_t n, i
                          double zp_host, int zp_learn, int qmin, int qmax, double gscale,
                          double *grad_out, double *ws, int64_t ws_len, uint32_t *counter,
                          void *stream);
+/*
+ * bf16 / fp16 activations (ABI 12).  The four entry points above with an element type:
+ * `dtype` (after n) is VSIQ_DT_F32 / _BF16 / _F16 and every tensor pointer (c, y, g, gc)
+ * holds elements of that type; everything else is the _f32 counterpart's argument.
+ *
+ * The rule: a typed call is its _f32 counterpart applied to the exactly widened inputs,
+ * with each tensor output of element type T (y, gc) rounded ONCE to T, round to nearest
+ * even.  All arithmetic is the fp32 / f64 code of the _f32 entry (nothing is computed in
+ * 16 bits); NaN stays NaN (payload unspecified), fp16 overflow gives +-inf, denormal
+ * results are kept.  Codes, the 1-bit mask (same word layout), qp_out, run_minmax, the
+ * stats record and grad_out are bit-identical to the _f32 call on the widened inputs: the
+ * grids, the accumulation order and the folds depend on n only.  (The reference never
+ * runs in half precision -- it calls .float() first -- so there is no per-op rounding to
+ * reproduce; this is what torch.fake_quantize_per_tensor_affine does for half inputs.)
+ *
+ *   - VSIQ_DT_F32 launches exactly what the _f32 entry launches.
+ *   - Another dtype returns VSIQ_E_ARG; n == 0 returns 0; null tensors with n > 0
+ *     return VSIQ_E_ARG; nothing launches on an error.
+ *   - Alignment is required of `mask` only.  A lane moves 4 elements per access (8 B of a
+ *     16-bit type) when n % 4 == 0 and the tensors are 8-byte aligned (16 for fp32);
+ *     other tensors take the scalar path, same results.
+ *   - vsiq_act_ste_bwd_t: 16-bit tensors in the per-tensor form only (one row: rowlen
+ *     <= 0, or == n); per-row scales return VSIQ_E_ARG.
+ * Every other entry point of this header is fp32-only.
+ */
+#define VSIQ_DT_F32 0
+#define VSIQ_DT_BF16 1
+#define VSIQ_DT_F16 2
+int vsiq_act_fq_fwd_t(const void *c, void *y, void *codes, uint64_t *mask, int64_t n, int dtype, int act,
+                      const double *qp_dev, const double *scale_dev, double scale_host,
+                      const double *zp_dev, double zp_host, int zp_round, int discrete, int qmin,
+                      int qmax, void *stream);
+int vsiq_act_observe_t(const void *c, int64_t n, int dtype, int act, double *stats_out, float *run_minmax,
+                       double *qp_out, int symmetric, double qden, double eps, double *ws,
+                       int64_t ws_len, uint32_t *counter, void *stream);
+int vsiq_act_ste_bwd_t(const void *g, const uint64_t *mask, const void *c, void *gc, int64_t n, int dtype,
+                       int act, const double *scale_dev, int64_t rowlen, double scale_host,
+                       void *stream);
+int vsiq_act_lsq_bwd_t(const void *g, const void *c, void *gc, int64_t n, int dtype, int act,
+                       const double *scale_dev, double scale_host, const double *zp_dev,
+                       double zp_host, int zp_learn, int qmin, int qmax, double gscale,
+                       double *grad_out, double *ws, int64_t ws_len, uint32_t *counter,
+                       void *stream);
 /*
  * The activation alone (K5's element code, same act argument): y = act(c) and its
  * backward gc = d act(c)/dc * g.  Replaces F.relu / F.silu of the fused layers

@@ -48,7 +48,8 @@ FLAGS = [
 # and k_lib.hip were one translation unit with it: their kernels keep the flag they were
 # built with.
 _NO_SLP = ["-fno-slp-vectorize"]
-FILE_FLAGS = {"k_observe.hip": _NO_SLP, "k_observe_fq.hip": _NO_SLP, "k_lib.hip": _NO_SLP}
+FILE_FLAGS = {"k_observe.hip": _NO_SLP, "k_observe_half.hip": _NO_SLP, "k_observe_fq.hip": _NO_SLP,
+              "k_lib.hip": _NO_SLP}
 
 
 def hipcc() -> str:

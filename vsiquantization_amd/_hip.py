@@ -25,7 +25,7 @@ c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
 c_d = ctypes.c_double
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 COUNTER_WORDS = 64   # VSIQ_COUNTER_WORDS
 COUNTER_GRID_ERRORS = 35   # VSIQ_COUNTER_GRID_ERRORS (K10's barrier-timeout count)
 
@@ -44,6 +44,7 @@ TUNE_XCD_ORDER = 13
 TUNE_K2O_FORM, TUNE_K2O_GROUPS, TUNE_K2O_BLOCK = 14, 15, 17
 REMOVED_TUNE_KEYS = (1, 5, 8, 16)   # ABI 10: K3 rows / workgroup size, K2 grid, K2 cached-load threshold
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
+DT_F32, DT_BF16, DT_F16 = 0, 1, 2   # VSIQ_DT_*: the element type of the typed (_t) entry points
 ACT_CODES = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "silu": ACT_SILU}
 
 # SiLU bit for bit as torch's CPU kernel on this host (include/vsiq.h VSIQ_ACT_SILU_REF):
@@ -241,6 +242,13 @@ _SIGS = {
     "vsiq_act_ste_bwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_int, c_p, c_i64, c_d, c_p], c_int),
     "vsiq_act_lsq_bwd_f32": ([c_p, c_p, c_p, c_i64, c_int, c_p, c_d, c_p, c_d, c_int, c_int, c_int, c_d,
                               c_p, c_p, c_i64, c_p, c_p], c_int),
+    "vsiq_act_fq_fwd_t": ([c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_d, c_p, c_d, c_int, c_int,
+                           c_int, c_int, c_p], c_int),
+    "vsiq_act_observe_t": ([c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_int, c_d, c_d, c_p, c_i64, c_p, c_p],
+                           c_int),
+    "vsiq_act_ste_bwd_t": ([c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_p, c_i64, c_d, c_p], c_int),
+    "vsiq_act_lsq_bwd_t": ([c_p, c_p, c_p, c_i64, c_int, c_int, c_p, c_d, c_p, c_d, c_int, c_int, c_int, c_d,
+                            c_p, c_p, c_i64, c_p, c_p], c_int),
 }
 EXPORTED = tuple(_SIGS)
 
@@ -358,6 +366,31 @@ def require_device_f32(x: torch.Tensor, what: str = "x") -> torch.Tensor:
     if x.dtype != torch.float32:
         raise TypeError(f"{what}: only float32 is supported by the HIP fake-quant path, got {x.dtype}")
     return x.contiguous()
+
+
+_DT_CODES = {torch.float32: DT_F32, torch.bfloat16: DT_BF16, torch.float16: DT_F16}
+
+
+def require_device_float(x: torch.Tensor, what: str = "x"):
+    """(contiguous x, VSIQ_DT_* code) of a CUDA float32 / bfloat16 / float16 tensor: the
+    argument check of the ops that have typed kernels (K1 / K5 forward, the per-tensor STE
+    backward, K4, the per-call observer).  Everything else stays behind require_device_f32."""
+    if isinstance(x, torch.Tensor) and x.device.type == "cuda" and x.dtype in _DT_CODES:
+        return x.contiguous(), _DT_CODES[x.dtype]
+    if isinstance(x, torch.Tensor) and x.device.type == "cpu" and x.dtype in (torch.bfloat16, torch.float16):
+        raise TypeError(f"{what}: only float32 is supported by the host (CPU) fake-quant path, got {x.dtype}")
+    if isinstance(x, torch.Tensor) and x.device.type == "cuda":
+        raise TypeError(f"{what}: float32, bfloat16 or float16 expected by the HIP fake-quant path, got {x.dtype}")
+    return require_device_f32(x, what), DT_F32   # raises: not a tensor / not on the GPU
+
+
+def require_same_dtype(t: torch.Tensor, ref: torch.Tensor, what: str) -> torch.Tensor:
+    """``t`` as a contiguous CUDA tensor of ``ref``'s dtype (grad_output / pre-activation of
+    a typed op): another dtype is a TypeError, never a silent cast."""
+    t, _ = require_device_float(t, what)
+    if t.dtype != ref.dtype:
+        raise TypeError(f"{what} is {t.dtype}, expected {ref.dtype} like the tensor it belongs to")
+    return t
 
 
 def mask_buffer(rows: int, rowlen: int, device) -> torch.Tensor:

@@ -53,6 +53,21 @@ decltype(auto) with_act(int act, F &&f) {
   return k == kActRelu ? f(IntC<kActRelu>{}) : k == kActSilu ? f(IntC<kActSilu>{}) : f(IntC<kActNone>{});
 }
 
+// the element type of a C ABI dtype argument (VSIQ_DT_*; dtype_ok checked it): f(TypeC<T>),
+// T = typename decltype(D)::type.  A site's 16-bit cases call functions that are explicitly
+// instantiated in the 16-bit translation units (k_*_half.hip), so the fp32 objects hold
+// fp32 kernels only.
+template <class T>
+struct TypeC {
+  using type = T;
+};
+inline bool dtype_ok(int dtype) { return dtype == VSIQ_DT_F32 || dtype == VSIQ_DT_BF16 || dtype == VSIQ_DT_F16; }
+
+template <class F>
+decltype(auto) with_dtype(int dtype, F &&f) {
+  return dtype == VSIQ_DT_BF16 ? f(TypeC<bf16_t>{}) : dtype == VSIQ_DT_F16 ? f(TypeC<f16_t>{}) : f(TypeC<float>{});
+}
+
 // f(VEC, NT) over (1,1), (1,0), (0,0): the scalar path has no non-temporal instance
 template <class F>
 decltype(auto) with_vec_nt(bool vec, bool nt, F &&f) {

@@ -19,8 +19,9 @@ __device__ __forceinline__ QP qp_of(const F &f) { return f(); }
 // ----------------------------------------------------------------------------
 // U groups per lane: kFlatU, or 9 for a one-round grid whose stores wait behind the
 // store gate (gc: gate_begin at the workgroup start; gate 0 = no gate).
-template <bool VEC, bool NT, bool CODES, bool MASK, int ACT, int U = kFlatU, class QF = QP>
-__device__ __forceinline__ void fq_fwd_block(const float *__restrict__ x, float *__restrict__ y,
+// T: the element type of x and y (float, bf16_t, f16_t; vsiq_common.cuh's accessors).
+template <bool VEC, bool NT, bool CODES, bool MASK, int ACT, int U = kFlatU, class QF = QP, typename T = float>
+__device__ __forceinline__ void fq_fwd_block(const T *__restrict__ x, T *__restrict__ y,
                                              uint8_t *__restrict__ codes, uint64_t *__restrict__ mask,
                                              int64_t n, const QF &qf, int64_t blk, GateClk gc = GateClk{0},
                                              uint32_t gate = 0, const SiluLay &L = SiluLay{}) {
@@ -236,8 +237,8 @@ __device__ __forceinline__ void lsq_group(float *gx, int64_t i, int64_t ng, int6
 // group k+kLsqPrefetch is loaded while group k computes, so x/g loads stay in flight
 // and s_waitcnt counts are exact.  Adds this thread's terms to c (not reduced) and
 // leaves grad_x in o[] (stored by lsq_store_block once the block has arrived).
-template <bool VEC, bool NT, bool ZPL, int ACT, int G, class QF = QP>
-__device__ __forceinline__ QP lsq_bwd_block(const float *__restrict__ g, const float *__restrict__ x,
+template <bool VEC, bool NT, bool ZPL, int ACT, int G, class QF = QP, typename T = float>
+__device__ __forceinline__ QP lsq_bwd_block(const T *__restrict__ g, const T *__restrict__ x,
                                             int64_t n, const QF &qf, int64_t blk, LsqAcc &c, f4 (&o)[G],
                                             const SiluLay &L = SiluLay{}) {
   const int64_t ng = cdiv(n, 4);
@@ -260,8 +261,8 @@ __device__ __forceinline__ QP lsq_bwd_block(const float *__restrict__ g, const f
   return p;
 }
 
-template <bool VEC, bool NT, int G>
-__device__ __forceinline__ void lsq_store_block(float *__restrict__ gx, int64_t n, int64_t blk, const f4 (&o)[G]) {
+template <bool VEC, bool NT, int G, typename T = float>
+__device__ __forceinline__ void lsq_store_block(T *__restrict__ gx, int64_t n, int64_t blk, const f4 (&o)[G]) {
   const int64_t ng = cdiv(n, 4);
   const int64_t base = blk * kBlock * G + threadIdx.x;
 #pragma unroll
@@ -273,8 +274,8 @@ __device__ __forceinline__ void lsq_store_block(float *__restrict__ gx, int64_t 
 // waves 1..3 store their grad_x and return false; wave 0 passes an LDS-only barrier
 // and gets the block record {sum t, sum z} (fixed order) in every lane.  STORE false:
 // the caller stored every wave's grad_x already (records-only K4d).
-template <bool VEC, bool NT, int G, bool STORE = true>
-__device__ __forceinline__ bool lsq_block_record(LsqAcc c, float *__restrict__ gx, int64_t n, int64_t blk,
+template <bool VEC, bool NT, int G, bool STORE = true, typename T = float>
+__device__ __forceinline__ bool lsq_block_record(LsqAcc c, T *__restrict__ gx, int64_t n, int64_t blk,
                                                  const f4 (&o)[G], double (&rec)[2]) {
   __shared__ double s[kWaves][2];
   c.t = wave_reduce(c.t, AddD());

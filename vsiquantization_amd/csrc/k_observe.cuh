@@ -187,8 +187,8 @@ __device__ __forceinline__ void observe_epilogue(ObsAcc &a, int64_t n, double *_
 // body shared by k_observe_loop and k_observe_part.
 // Block `blk` of an `nblk`-block grid over x (the multi-tensor K2m runs the same body
 // on its tensors' block ranges).
-template <bool VEC, bool NT, int ACT, int U>
-__device__ __forceinline__ void observe_stride_b(const float *__restrict__ x, int64_t n, ObsAcc &a,
+template <bool VEC, bool NT, int ACT, int U, typename T = float>
+__device__ __forceinline__ void observe_stride_b(const T *__restrict__ x, int64_t n, ObsAcc &a,
                                                  int64_t blk, int64_t nblk, const SiluLay &L) {
   obs_init(a);
   const int64_t ng = cdiv(n, 4);
@@ -201,7 +201,7 @@ __device__ __forceinline__ void observe_stride_b(const float *__restrict__ x, in
       // 32-bit lane offsets (no per-group 64-bit clamp / address arithmetic: -16 VGPRs,
       // -40 instructions per step at U = 8), straight-line, no per-group exec-mask
       // branches (they were ~1/3 of the K2p instruction stream)
-      const float *xb = x + 4 * b;
+      const T *xb = x + 4 * b;
 #pragma unroll
       for (int k = 0; k < U; ++k) v[k] = ld4<NT>(xb + 4 * (threadIdx.x + k * kBlock));
 #pragma unroll

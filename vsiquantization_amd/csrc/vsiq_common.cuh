@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "vsiq.h"
 
@@ -627,35 +628,100 @@ __device__ __forceinline__ QP load_qp(const QPSrc &a) {
 }
 
 // ----------------------------------------------------------------------------
-// streamed memory access: 16 B per lane, optional nontemporal hint
+// streamed memory access: 4 elements per lane (16 B of fp32, 8 B of bf16 / fp16),
+// optional nontemporal hint.  The element type T is the tensor's; every accessor hands
+// the arithmetic an f4: a 16-bit T is widened (exactly) after the load and narrowed
+// (once, round-to-nearest-even) before the store, in registers.
 // ----------------------------------------------------------------------------
-template <bool NT>
-__device__ __forceinline__ f4 ld4(const float *p) {
-  const f4 *q = reinterpret_cast<const f4 *>(p);
-  if (NT) return __builtin_nontemporal_load(q);
-  return *q;
+typedef __bf16 bf16_t;
+typedef _Float16 f16_t;
+typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+typedef f16_t h2 __attribute__((ext_vector_type(2)));
+typedef bf16_t b2 __attribute__((ext_vector_type(2)));
+
+template <typename T>
+inline constexpr bool kIsElem = std::is_same_v<T, float> || std::is_same_v<T, bf16_t> || std::is_same_v<T, f16_t>;
+
+// the two 16-bit elements of a dword -> fp32 (bf16: the bits are the fp32's upper half)
+template <typename T>
+__device__ __forceinline__ void widen2(uint32_t w, float &a, float &b) {
+  if constexpr (std::is_same_v<T, bf16_t>) {
+    a = u2f(w << 16);
+    b = u2f(w & 0xffff0000u);
+  } else {
+    const h2 h = __builtin_bit_cast(h2, w);
+    a = (float)h.x;
+    b = (float)h.y;
+  }
+}
+
+// RNE(a), RNE(b) packed into a dword (gfx950: v_cvt_pk_bf16_f32 / v_cvt_f16_f32);
+// NaN stays NaN, fp16 overflow gives +-inf, denormal results are kept
+template <typename T>
+__device__ __forceinline__ uint32_t narrow2(float a, float b) {
+  if constexpr (std::is_same_v<T, bf16_t>) {
+    b2 o;
+    o.x = (bf16_t)a;
+    o.y = (bf16_t)b;
+    return __builtin_bit_cast(uint32_t, o);
+  } else {
+    h2 o;
+    o.x = (f16_t)a;
+    o.y = (f16_t)b;
+    return __builtin_bit_cast(uint32_t, o);
+  }
+}
+
+template <bool NT, typename T = float>
+__device__ __forceinline__ f4 ld4(const T *p) {
+  static_assert(kIsElem<T>, "element type");
+  if constexpr (std::is_same_v<T, float>) {
+    const f4 *q = reinterpret_cast<const f4 *>(p);
+    if (NT) return __builtin_nontemporal_load(q);
+    return *q;
+  } else {
+    const u2 *q = reinterpret_cast<const u2 *>(p);
+    const u2 w = NT ? __builtin_nontemporal_load(q) : *q;
+    float a, b, c, d;
+    widen2<T>(w.x, a, b);
+    widen2<T>(w.y, c, d);
+    f4 v;
+    v.x = a; v.y = b; v.z = c; v.w = d;
+    return v;
+  }
 }
 // (measured on MI355X, C2 step: write-through sc1 / sc0 sc1 / nt sc1 and plain stores are
 // 0.1-4 us slower per launch than nt stores, in K3 and the STE backward alike)
-template <bool NT>
-__device__ __forceinline__ void st4(float *p, f4 v) {
-  f4 *q = reinterpret_cast<f4 *>(p);
-  if (NT) __builtin_nontemporal_store(v, q);
-  else *q = v;
+template <bool NT, typename T = float>
+__device__ __forceinline__ void st4(T *p, f4 v) {
+  static_assert(kIsElem<T>, "element type");
+  if constexpr (std::is_same_v<T, float>) {
+    f4 *q = reinterpret_cast<f4 *>(p);
+    if (NT) __builtin_nontemporal_store(v, q);
+    else *q = v;
+  } else {
+    u2 w;
+    w.x = narrow2<T>(v.x, v.y);
+    w.y = narrow2<T>(v.z, v.w);
+    u2 *q = reinterpret_cast<u2 *>(p);
+    if (NT) __builtin_nontemporal_store(w, q);
+    else *q = w;
+  }
 }
 
 // A group of 4 consecutive elements of a row starting at element 4*i.
-// VEC: one 16-B access (row length % 4 == 0, 16-B aligned).  Otherwise 4 scalar
-// accesses with per-element bounds ("virtual float4"); invalid lanes replicate
-// element 0 so min/max/NaN see no fake values.
-template <bool VEC, bool NT>
-__device__ __forceinline__ f4 load_group(const float *row, int64_t i, int64_t len) {
+// VEC: one access of 4 elements (row length % 4 == 0; 16-B aligned fp32, 8-B aligned
+// 16-bit).  Otherwise 4 scalar accesses with per-element bounds ("virtual float4");
+// invalid lanes replicate element 0 so min/max/NaN see no fake values.
+template <bool VEC, bool NT, typename T = float>
+__device__ __forceinline__ f4 load_group(const T *row, int64_t i, int64_t len) {
   if (VEC) return ld4<NT>(row + 4 * i);
   // unconditional (clamped) scalar loads keep the vmcnt bookkeeping exact
   const int64_t e = 4 * i, l = len - 1;
   f4 v;
-  v.x = row[e];
-  const float y = row[e + 1 < l ? e + 1 : l], z = row[e + 2 < l ? e + 2 : l], w = row[e + 3 < l ? e + 3 : l];
+  v.x = (float)row[e];
+  const float y = (float)row[e + 1 < l ? e + 1 : l], z = (float)row[e + 2 < l ? e + 2 : l],
+              w = (float)row[e + 3 < l ? e + 3 : l];
   v.y = e + 1 < len ? y : v.x;
   v.z = e + 2 < len ? z : v.x;
   v.w = e + 3 < len ? w : v.x;
@@ -664,22 +730,22 @@ __device__ __forceinline__ f4 load_group(const float *row, int64_t i, int64_t le
 
 // group i clamped into [0, ng): loads are issued unconditionally (no branch around a
 // load, so hipcc's s_waitcnt counting stays exact); callers predicate the stores
-template <bool VEC, bool NT>
-__device__ __forceinline__ f4 load_group_c(const float *row, int64_t i, int64_t ng, int64_t len) {
+template <bool VEC, bool NT, typename T = float>
+__device__ __forceinline__ f4 load_group_c(const T *row, int64_t i, int64_t ng, int64_t len) {
   return load_group<VEC, NT>(row, i < ng ? i : ng - 1, len);
 }
 
-template <bool VEC, bool NT>
-__device__ __forceinline__ void store_group(float *row, int64_t i, int64_t len, f4 v) {
+template <bool VEC, bool NT, typename T = float>
+__device__ __forceinline__ void store_group(T *row, int64_t i, int64_t len, f4 v) {
   if (VEC) {
     st4<NT>(row + 4 * i, v);
     return;
   }
   const int64_t e = 4 * i;
-  row[e] = v.x;
-  if (e + 1 < len) row[e + 1] = v.y;
-  if (e + 2 < len) row[e + 2] = v.z;
-  if (e + 3 < len) row[e + 3] = v.w;
+  row[e] = (T)v.x;
+  if (e + 1 < len) row[e + 1] = (T)v.y;
+  if (e + 2 < len) row[e + 2] = (T)v.z;
+  if (e + 3 < len) row[e + 3] = (T)v.w;
 }
 
 __device__ __forceinline__ int valid_in_group(int64_t i, int64_t len) {
@@ -803,8 +869,8 @@ __device__ __forceinline__ void mask_put(uint32_t &lo, uint32_t &hi, int slot, c
   }
 }
 
-template <bool VEC, bool NT, bool CODES>
-__device__ __forceinline__ void fq_store_out(float *yr, uint8_t *cr, int64_t i, int64_t ng, int64_t len,
+template <bool VEC, bool NT, bool CODES, typename T = float>
+__device__ __forceinline__ void fq_store_out(T *yr, uint8_t *cr, int64_t i, int64_t ng, int64_t len,
                                              const GroupOut &g) {
   if (i < ng) {
     store_group<VEC, NT>(yr, i, len, g.o);
@@ -1257,6 +1323,9 @@ __host__ __device__ __forceinline__ void observer_update(float cmn, float cmx, b
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 inline bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 inline bool aligned8(const void *p) { return ((uintptr_t)p & 7u) == 0; }
+// a tensor of T takes the vector path (4 elements per access) from this alignment on
+template <typename T>
+inline bool aligned_vec(const void *p) { return ((uintptr_t)p & (4 * sizeof(T) - 1)) == 0; }
 
 // Deferred store phase.  A grid that streams its whole input in one round (every
 // workgroup resident at once, all loads issued at t = 0) runs faster on MI355X's HBM3E

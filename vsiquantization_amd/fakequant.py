@@ -71,6 +71,8 @@ def fake_quant(x: torch.Tensor, scale, zero_point, qmin: int, qmax: int, *, zp_r
                qp: torch.Tensor | None = None, want_mask: bool = False, want_codes: bool = False,
                discrete: bool = False, act=None):
     """y = (clamp(rint(x/s + zp), qmin, qmax) - zp) * s  (uniform.py:55,95), fp32, bit-exact.
+    A CUDA bfloat16 / float16 x: the fp32 result on the exactly widened x, rounded once
+    (to nearest even) into y of x's dtype; mask and codes are the fp32 call's.
 
     qp: optional observer record (f64[QP_LEN] on x.device) used instead of scale/zero_point.
     discrete: return the integer-valued fp32 codes in y instead (discreate_tensor).
@@ -79,7 +81,7 @@ def fake_quant(x: torch.Tensor, scale, zero_point, qmin: int, qmax: int, *, zp_r
     if _host.is_host(x):
         return _host.fake_quant(x, scale, zero_point, qmin, qmax, zp_round=zp_round, qp=qp, want_mask=want_mask,
                                 want_codes=want_codes, discrete=discrete, act=act)
-    x = H.require_device_f32(x)
+    x, dt = H.require_device_float(x)
     dev = x.device
     y = torch.empty_like(x)
     mask = H.mask_buffer(1, x.numel(), dev) if want_mask else None
@@ -91,34 +93,36 @@ def fake_quant(x: torch.Tensor, scale, zero_point, qmin: int, qmax: int, *, zp_r
     else:
         sd, sh = scalar_source(scale, dev)
         zd, zh = scalar_source(zero_point, dev)
-    rc = H.lib().vsiq_act_fq_fwd_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(x.numel()),
-                                     H.act_code(act), H.ptr(qp), H.ptr(sd), sh, H.ptr(zd), zh,
-                                     int(bool(zp_round)), int(bool(discrete)), int(qmin), int(qmax),
-                                     H.stream_of(dev))
-    H.check(rc, "vsiq_act_fq_fwd_f32")
+    rc = H.lib().vsiq_act_fq_fwd_t(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(x.numel()), dt,
+                                   H.act_code(act), H.ptr(qp), H.ptr(sd), sh, H.ptr(zd), zh,
+                                   int(bool(zp_round)), int(bool(discrete)), int(qmin), int(qmax),
+                                   H.stream_of(dev))
+    H.check(rc, "vsiq_act_fq_fwd_t")
     return y, mask, codes
 
 
 def ste_backward(g: torch.Tensor, mask: torch.Tensor, scale, rowlen: int = 0, *, pre=None,
                  act=None) -> torch.Tensor:
     """gx = (mask ? g*s : 0) / s  — autograd of uniform.py:55,95 with a fixed scale;
-    with ``act``, the activation's backward at the pre-activation ``pre`` follows."""
-    g = H.require_device_f32(g, "grad_output")
+    with ``act``, the activation's backward at the pre-activation ``pre`` follows.
+    bfloat16 / float16 g (per-tensor form only; ``pre`` of g's dtype): fake_quant's rule."""
+    g, dt = H.require_device_float(g, "grad_output")
     a = H.act_code(act)
     if a != H.ACT_NONE:
-        pre = H.require_device_f32(pre, "pre-activation")
+        pre = H.require_same_dtype(pre, g, "pre-activation")
         if pre.shape != g.shape:
             raise ValueError(f"pre-activation shape {tuple(pre.shape)} != grad shape {tuple(g.shape)}")
     dev = g.device
     gx = torch.empty_like(g)
     if isinstance(scale, torch.Tensor) and scale.device.type == "cuda" and scale.numel() > 1:
+        g = H.require_device_f32(g, "grad_output")   # per-row scales: fp32 kernels only
         sd, sh = scale.detach().to(torch.float64).contiguous(), 0.0
     else:
         sd, sh = scalar_source(scale, dev)
         rowlen = 0
-    rc = H.lib().vsiq_act_ste_bwd_f32(H.ptr(g), H.ptr(mask), H.ptr(pre if a else None), H.ptr(gx),
-                                      _i64(g.numel()), a, H.ptr(sd), _i64(rowlen), sh, H.stream_of(dev))
-    H.check(rc, "vsiq_act_ste_bwd_f32")
+    rc = H.lib().vsiq_act_ste_bwd_t(H.ptr(g), H.ptr(mask), H.ptr(pre if a else None), H.ptr(gx),
+                                    _i64(g.numel()), dt, a, H.ptr(sd), _i64(rowlen), sh, H.stream_of(dev))
+    H.check(rc, "vsiq_act_ste_bwd_t")
     return gx
 
 
@@ -168,6 +172,7 @@ class FakeQuantFixedFn(torch.autograd.Function):
     def forward(ctx, x, scale, zero_point, qmin, qmax, qp, act=None):
         y, mask, _ = fake_quant(x, scale, zero_point, qmin, qmax, qp=qp, want_mask=True, act=act)
         ctx.act = act
+        ctx.dtype = x.dtype
         if H.act_code(act) != H.ACT_NONE:
             ctx.save_for_backward(mask, x)
         else:
@@ -182,8 +187,16 @@ class FakeQuantFixedFn(torch.autograd.Function):
     def backward(ctx, gy):
         saved = ctx.saved_tensors
         pre = saved[1] if len(saved) > 1 else None
+        if gy.dtype != ctx.dtype:
+            raise TypeError(f"grad_output is {gy.dtype}, the fake-quantized tensor was {ctx.dtype}")
         gx = ste_backward(gy.contiguous(), saved[0], ctx.scale, pre=pre, act=ctx.act)
         return gx, None, None, None, None, None, None
+
+
+def _is_half(x) -> bool:
+    """A CUDA bfloat16 / float16 tensor: served by the typed kernels through the Python
+    autograd Functions."""
+    return isinstance(x, torch.Tensor) and x.device.type == "cuda" and x.dtype in (torch.bfloat16, torch.float16)
 
 
 def _qarg(v):
@@ -199,12 +212,13 @@ def _qarg(v):
 
 def fake_quant_fixed(x, scale, zero_point, qmin, qmax, qp=None, act=None):
     """Fixed-qparam fake quant; with a gradient-requiring x, the STE backward is attached
-    (C++ node of _vsiq_torch.so, or FakeQuantFixedFn with VSIQ_TORCH_EXT=0).  CPU tensors:
+    (C++ node of _vsiq_torch.so, or FakeQuantFixedFn with VSIQ_TORCH_EXT=0; the C++ nodes
+    are fp32-only, so a bfloat16 / float16 x always takes FakeQuantFixedFn).  CPU tensors:
     the native host path (host.py)."""
     if _host.is_host(x):
         return _host.fake_quant_fixed(x, scale, zero_point, qmin, qmax, qp=qp, act=act)
     if x.requires_grad and torch.is_grad_enabled():
-        if H.torch_ext_enabled():
+        if H.torch_ext_enabled() and not _is_half(x):
             x = H.require_device_f32(x)
             st, sh = _qarg(scale) if qp is None else (None, 0.0)
             zt, zh = _qarg(zero_point) if qp is None else (None, 0.0)
@@ -216,10 +230,11 @@ def fake_quant_fixed(x, scale, zero_point, qmin, qmax, qp=None, act=None):
 def fake_quant_learn(x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None):
     """Learnable fake quant (uniform.py:47-56): K1/K5 forward, K4 backward with the
     ScaleGradient factor ``gscale`` (C++ node of _vsiq_torch.so, or FakeQuantLearnFn
-    with VSIQ_TORCH_EXT=0).  CPU tensors: the native host path (host.py)."""
+    with VSIQ_TORCH_EXT=0 or a bfloat16 / float16 x).  CPU tensors: the native host path
+    (host.py)."""
     if _host.is_host(x):
         return _host.fake_quant_learn(x, scale, zero_point, qmin, qmax, gscale, learn_zp, act)
-    if H.torch_ext_enabled() and learn_zp != 2:   # the C++ node takes its K4 workspace from its own cache
+    if H.torch_ext_enabled() and learn_zp != 2 and not _is_half(x):   # the C++ node takes its K4 workspace from its own cache
         x = H.require_device_f32(x)
         st, sh = _qarg(scale)
         zt, zh = _qarg(zero_point)
@@ -231,19 +246,22 @@ def fake_quant_learn(x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=Non
 # --------------------------------------------------------------------------- learnable (K4)
 def lsq_backward(g, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None):
     """K4: (grad_x, f64[2] {grad_scale, grad_zp}); with ``act``, x is the pre-activation
-    and grad_x goes through the activation's backward."""
-    g = H.require_device_f32(g, "grad_output")
+    and grad_x goes through the activation's backward.  bfloat16 / float16 g and x (the
+    same dtype): fake_quant's rule; the f64 gradients are the fp32 call's on the widened
+    tensors, bit for bit."""
+    g, dt = H.require_device_float(g, "grad_output")
+    x = H.require_same_dtype(x, g, "x")
     dev = g.device
     gx = torch.empty_like(g)
     grads = torch.empty(2, dtype=torch.float64, device=dev)
     sd, sh = scalar_source(scale, dev)
     zd, zh = scalar_source(zero_point, dev)
     w = H.workspace(dev, g.numel())
-    rc = H.lib().vsiq_act_lsq_bwd_f32(H.ptr(g), H.ptr(x), H.ptr(gx), _i64(g.numel()), H.act_code(act),
-                                      H.ptr(sd), sh, H.ptr(zd), zh, int(learn_zp), int(qmin),
-                                      int(qmax), float(gscale), H.ptr(grads), H.ptr(w.ws),
-                                      _i64(w.ws_len), H.ptr(w.counter), H.stream_of(dev))
-    H.check(rc, "vsiq_act_lsq_bwd_f32")
+    rc = H.lib().vsiq_act_lsq_bwd_t(H.ptr(g), H.ptr(x), H.ptr(gx), _i64(g.numel()), dt, H.act_code(act),
+                                    H.ptr(sd), sh, H.ptr(zd), zh, int(learn_zp), int(qmin),
+                                    int(qmax), float(gscale), H.ptr(grads), H.ptr(w.ws),
+                                    _i64(w.ws_len), H.ptr(w.counter), H.stream_of(dev))
+    H.check(rc, "vsiq_act_lsq_bwd_t")
     return gx, grads
 
 
@@ -255,7 +273,7 @@ class FakeQuantLearnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None):
-        x = H.require_device_f32(x)
+        x, _ = H.require_device_float(x)
         y, _, _ = fake_quant(x, scale, zero_point, qmin, qmax, zp_round=learn_zp == 1, act=act)
         ctx.save_for_backward(x)
         ctx.scale, ctx.zp = scale, zero_point
@@ -267,6 +285,8 @@ class FakeQuantLearnFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         qmin, qmax, gscale, learn_zp, act = ctx.args
         s, z = ctx.scale, ctx.zp
+        if gy.dtype != x.dtype:
+            raise TypeError(f"grad_output is {gy.dtype}, the fake-quantized tensor was {x.dtype}")
         gx, grads = lsq_backward(gy.contiguous(), x, s, z, qmin, qmax, gscale, learn_zp, act=act)
         gs = gz = None
         if isinstance(s, torch.Tensor) and ctx.needs_input_grad[1]:
@@ -402,22 +422,23 @@ def observe_tensor(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, eps: 
     """One pass over x: min/max/NaN/sums -> running state update -> f64 qparams (no sync).
 
     Returns (qp f64[QP_LEN] | None, stats f64[ST_LEN] | None).  CPU tensors: the native
-    host path (host.py; run_minmax a CPU fp32[2])."""
+    host path (host.py; run_minmax a CPU fp32[2]).  A CUDA bfloat16 / float16 x: the
+    record, state and qparams of the fp32 call on the widened values, bit for bit."""
     if _host.is_host(x):
         return _host.observe_tensor(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=run_minmax,
                                     want_qp=want_qp, want_stats=want_stats, act=act)
-    x = H.require_device_f32(x)
+    x, dt = H.require_device_float(x)
     if x.numel() == 0:
         raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
     dev = x.device
     qp = torch.empty(H.QP_LEN, dtype=torch.float64, device=dev) if want_qp else None
     st = torch.empty(H.ST_LEN, dtype=torch.float64, device=dev) if want_stats else None
     w = H.workspace(dev, x.numel())
-    rc = H.lib().vsiq_act_observe_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), H.ptr(st),
-                                      H.ptr(run_minmax), H.ptr(qp), int(bool(symmetric)),
-                                      qden(symmetric, num_bits, eps), float(eps), H.ptr(w.ws),
-                                      _i64(w.ws_len), H.ptr(w.counter), H.stream_of(dev))
-    H.check(rc, "vsiq_act_observe_f32")
+    rc = H.lib().vsiq_act_observe_t(H.ptr(x), _i64(x.numel()), dt, H.act_code(act), H.ptr(st),
+                                    H.ptr(run_minmax), H.ptr(qp), int(bool(symmetric)),
+                                    qden(symmetric, num_bits, eps), float(eps), H.ptr(w.ws),
+                                    _i64(w.ws_len), H.ptr(w.counter), H.stream_of(dev))
+    H.check(rc, "vsiq_act_observe_t")
     return qp, st
 
 

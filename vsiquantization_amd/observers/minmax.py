@@ -130,7 +130,7 @@ class MinMaxObserver(BaseObserver):
         if host.is_host(x):   # CPU tensor: the native host pass (host.py), CPU fp32[2] state
             dev = x.device
         else:
-            dev = H.require_device_f32(x).device
+            dev = H.require_device_float(x)[0].device   # fp32, or bf16 / fp16 (typed K2)
             if self._obs_stream is not None and self._obs_stream != torch.cuda.current_stream(dev):
                 self._join()
         state = self.device_state(dev)
