@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define VSIQ_ABI_VERSION 12
+#define VSIQ_ABI_VERSION 13
 
 /* uint32 words of a reducing kernel's arrival `counter` (all 0 before the first call) */
 #define VSIQ_COUNTER_WORDS 64
@@ -485,6 +485,9 @@ int vsiq_lsq_bwd_multi_f32(const vsiq_lsq_tensor *tensors, int count, double *ws
  * as its scratch (their contents are overwritten).  The activation quantizers of a QAT model (quantize_out of every fused
  * layer, fake_quantize.py:49-50 -> uniform.py:47-56) are folded in one launch when
  * autograd has been through all of them (quantizers/deferred.py).
+ * bf16 / fp16 tensors (ABI 13): vsiq_act_lsq_bwd_part_t, declared with the typed entry
+ * points below; its records are the fp32 call's, so one vsiq_lsq_fold_multi launch folds
+ * typed and fp32 calls together.
  */
 typedef struct vsiq_lsq_fold {
   double *records;         /* the call's records, nrec x {sum t, sum z} (overwritten) */
@@ -542,7 +545,7 @@ int vsiq_act_lsq_bwd_f32(const float *g, const float *c, float *gc, int64_t n, i
                          double *grad_out, double *ws, int64_t ws_len, uint32_t *counter,
                          void *stream);
 /*
- * bf16 / fp16 activations (ABI 12).  The four entry points above with an element type:
+ * bf16 / fp16 activations (ABI 12; K4d since ABI 13).  Entry points above with an element type:
  * `dtype` (after n) is VSIQ_DT_F32 / _BF16 / _F16 and every tensor pointer (c, y, g, gc)
  * holds elements of that type; everything else is the _f32 counterpart's argument.
  *
@@ -564,6 +567,15 @@ int vsiq_act_lsq_bwd_f32(const float *g, const float *c, float *gc, int64_t n, i
  *     other tensors take the scalar path, same results.
  *   - vsiq_act_ste_bwd_t: 16-bit tensors in the per-tensor form only (one row: rowlen
  *     <= 0, or == n); per-row scales return VSIQ_E_ARG.
+ *
+ * vsiq_act_lsq_bwd_part_t (ABI 13) is vsiq_act_lsq_bwd_part_f32 (K4d, above) under the same
+ * rule: gc rounded once to T; the vsiq_lsq_part_records(n) records {sum t, sum z} are
+ * bit-identical to the _f32 call on the widened inputs, on the vector path and on the
+ * scalar path, because their count and layout depend on n and VSIQ_TUNE_LSQ_GROUPS only
+ * (a record whose sum is NaN is the canonical quiet NaN, in the _f32 entry as well).
+ * Arguments are checked in the _f32 entry's order (records_len < 2 * records: VSIQ_E_WS;
+ * zp_learn outside 0 / 1: VSIQ_E_ARG).  vsiq_lsq_fold_multi never sees the element type.
+ *
  * Every other entry point of this header is fp32-only.
  */
 #define VSIQ_DT_F32 0
@@ -584,6 +596,11 @@ int vsiq_act_lsq_bwd_t(const void *g, const void *c, void *gc, int64_t n, int dt
                        double zp_host, int zp_learn, int qmin, int qmax, double gscale,
                        double *grad_out, double *ws, int64_t ws_len, uint32_t *counter,
                        void *stream);
+int vsiq_act_lsq_bwd_part_t(const void *g, const void *c, void *gc, int64_t n, int dtype, int act,
+                            const double *scale_dev, double scale_host, const double *zp_dev, double zp_host,
+                            int zp_learn, int qmin, int qmax,
+                            double *records,   // 2 * vsiq_lsq_part_records(n) doubles, as for _part_f32
+                            int64_t records_len, void *stream);
 /*
  * The activation alone (K5's element code, same act argument): y = act(c) and its
  * backward gc = d act(c)/dc * g.  Replaces F.relu / F.silu of the fused layers

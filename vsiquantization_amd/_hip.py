@@ -25,7 +25,7 @@ c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
 c_d = ctypes.c_double
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 COUNTER_WORDS = 64   # VSIQ_COUNTER_WORDS
 COUNTER_GRID_ERRORS = 35   # VSIQ_COUNTER_GRID_ERRORS (K10's barrier-timeout count)
 
@@ -249,6 +249,8 @@ _SIGS = {
     "vsiq_act_ste_bwd_t": ([c_p, c_p, c_p, c_p, c_i64, c_int, c_int, c_p, c_i64, c_d, c_p], c_int),
     "vsiq_act_lsq_bwd_t": ([c_p, c_p, c_p, c_i64, c_int, c_int, c_p, c_d, c_p, c_d, c_int, c_int, c_int, c_d,
                             c_p, c_p, c_i64, c_p, c_p], c_int),
+    "vsiq_act_lsq_bwd_part_t": ([c_p, c_p, c_p, c_i64, c_int, c_int, c_p, c_d, c_p, c_d, c_int, c_int, c_int, c_p,
+                                 c_i64, c_p], c_int),
 }
 EXPORTED = tuple(_SIGS)
 
@@ -374,7 +376,7 @@ _DT_CODES = {torch.float32: DT_F32, torch.bfloat16: DT_BF16, torch.float16: DT_F
 def require_device_float(x: torch.Tensor, what: str = "x"):
     """(contiguous x, VSIQ_DT_* code) of a CUDA float32 / bfloat16 / float16 tensor: the
     argument check of the ops that have typed kernels (K1 / K5 forward, the per-tensor STE
-    backward, K4, the per-call observer).  Everything else stays behind require_device_f32."""
+    backward, K4 and its records-only form K4d, the per-call observer).  Everything else stays behind require_device_f32."""
     if isinstance(x, torch.Tensor) and x.device.type == "cuda" and x.dtype in _DT_CODES:
         return x.contiguous(), _DT_CODES[x.dtype]
     if isinstance(x, torch.Tensor) and x.device.type == "cpu" and x.dtype in (torch.bfloat16, torch.float16):

@@ -41,8 +41,11 @@ __device__ __forceinline__ void lsq_bwd_body(const T *__restrict__ g, const T *_
     double rec[2];
     if (!lsq_block_record<VEC, NT, G, false>(c, gx, n, blockIdx.x, o, rec)) return;
     if (threadIdx.x == 0) {
-      ws[2 * (int64_t)blockIdx.x] = rec[0];
-      ws[2 * (int64_t)blockIdx.x + 1] = rec[1];
+      // a NaN sum leaves as the canonical quiet NaN: which operand's payload an add of two
+      // NaNs keeps depends on the operand order the compiler picked for this instance, and
+      // the records of a 16-bit call are the fp32 call's bits for NaN sums too
+      ws[2 * (int64_t)blockIdx.x] = rec[0] != rec[0] ? __builtin_nan("") : rec[0];
+      ws[2 * (int64_t)blockIdx.x + 1] = rec[1] != rec[1] ? __builtin_nan("") : rec[1];
     }
     return;
   }
@@ -60,7 +63,8 @@ __device__ __forceinline__ void lsq_bwd_body(const T *__restrict__ g, const T *_
 }
 
 // The fp32 kernel keeps its name and signature (saved gate tables and kernel traces name
-// it); k_lsq_bwd_t is the same body on 16-bit tensors (never PART: K4d stays fp32-only).
+// it); k_lsq_bwd_t is the same body on 16-bit tensors and k_lsq_bwd_part_t its records-only
+// (PART) form -- a kernel of its own, so k_lsq_bwd_t's symbols stay what they were.
 template <bool VEC, bool NT, bool ZPL, int ACT, int G, bool PART = false>
 __global__ __launch_bounds__(kBlock) void k_lsq_bwd(const float *__restrict__ g,
                                                     const float *__restrict__ x,
@@ -83,34 +87,48 @@ __global__ __launch_bounds__(kBlock) void k_lsq_bwd_t(const T *__restrict__ g, c
 }
 
 template <typename T, bool VEC, bool NT, bool ZPL, int ACT, int G>
+__global__ __launch_bounds__(kBlock) void k_lsq_bwd_part_t(const T *__restrict__ g, const T *__restrict__ x,
+                                                           T *__restrict__ gx, int64_t n, QPSrc src,
+                                                           double gscale, SiluLay L,
+                                                           double *__restrict__ grad_out,
+                                                           double *__restrict__ ws,
+                                                           uint32_t *__restrict__ counter, uint32_t gate) {
+  lsq_bwd_body<VEC, NT, ZPL, ACT, G, true>(g, x, gx, n, src, gscale, L, grad_out, ws, counter, gate);
+}
+
+template <typename T, bool VEC, bool NT, bool ZPL, int ACT, int G>
 constexpr auto lsq_bwd_kernel() {
   if constexpr (std::is_same_v<T, float>) return &k_lsq_bwd<VEC, NT, ZPL, ACT, G>;
   else return &k_lsq_bwd_t<T, VEC, NT, ZPL, ACT, G>;
+}
+
+template <typename T, bool VEC, bool NT, bool ZPL, int ACT, int G>
+constexpr auto lsq_bwd_part_kernel() {
+  if constexpr (std::is_same_v<T, float>) return &k_lsq_bwd<VEC, NT, ZPL, ACT, G, true>;
+  else return &k_lsq_bwd_part_t<T, VEC, NT, ZPL, ACT, G>;
 }
 
 template <int ACT, bool VEC, bool NT, int G, typename T>
 void launch_lsq_g(const T *g, const T *x, T *gx, int64_t n, const QPSrc &src, int zpl,
                   double gscale, double *grad_out, double *ws, uint32_t *counter, int64_t grid,
                   const SiluLay &L, hipStream_t st) {
-  if constexpr (std::is_same_v<T, float>) if (!counter) {   // records only (PART)
+  if (!counter) {   // records only (PART)
     // a one-round grid (store_gate_select takes grids of 2..occ workgroups per CU only):
-    // the tuned store gate between the read and the write phase
-    GateSel gs;
-    {
-      const void *kern = zpl ? reinterpret_cast<const void *>(k_lsq_bwd<VEC, NT, true, ACT, G, true>)
-                             : reinterpret_cast<const void *>(k_lsq_bwd<VEC, NT, false, ACT, G, true>);
-      static const int occ_t = occupancy_blocks(reinterpret_cast<const void *>(k_lsq_bwd<VEC, NT, true, ACT, G, true>),
-                                                kBlock);
-      static const int occ_f = occupancy_blocks(
-          reinterpret_cast<const void *>(k_lsq_bwd<VEC, NT, false, ACT, G, true>), kBlock);
-      gs = store_gate_select("k4d_lsq_bwd_part", kern, grid, zpl ? occ_t : occ_f, 8 * n, st);
-    }
+    // the tuned store gate between the read and the write phase.  One site label for
+    // every T; the read bytes (x and g) and the occupancy are the instance's own.
+    const auto kt = lsq_bwd_part_kernel<T, VEC, NT, true, ACT, G>();
+    const auto kf = lsq_bwd_part_kernel<T, VEC, NT, false, ACT, G>();
+    static const int occ_t = occupancy_blocks(reinterpret_cast<const void *>(kt), kBlock);
+    static const int occ_f = occupancy_blocks(reinterpret_cast<const void *>(kf), kBlock);
+    const void *kern = zpl ? reinterpret_cast<const void *>(kt) : reinterpret_cast<const void *>(kf);
+    GateSel gs = store_gate_select("k4d_lsq_bwd_part", kern, grid, zpl ? occ_t : occ_f,
+                                   2 * (int64_t)sizeof(T) * n, st);
     if (zpl)
-      hipLaunchKernelGGL((k_lsq_bwd<VEC, NT, true, ACT, G, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, g,
-                         x, gx, n, src, gscale, L, grad_out, ws, counter, gs.gate);
+      hipLaunchKernelGGL(kt, dim3((unsigned)grid), dim3(kBlock), 0, st, g, x, gx, n, src, gscale, L, grad_out, ws,
+                         counter, gs.gate);
     else
-      hipLaunchKernelGGL((k_lsq_bwd<VEC, NT, false, ACT, G, true>), dim3((unsigned)grid), dim3(kBlock), 0, st, g,
-                         x, gx, n, src, gscale, L, grad_out, ws, counter, gs.gate);
+      hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(kBlock), 0, st, g, x, gx, n, src, gscale, L, grad_out, ws,
+                         counter, gs.gate);
     store_gate_launched(gs, st);
     return;
   }
@@ -175,10 +193,35 @@ int lsq_bwd(const T *g, const T *x, T *gx, int64_t n, int act, const double *sca
   return launch_rc();
 }
 
+// Records-only K4 (PART, K4d): lsq_bwd's per-element code and block records on a grid of
+// lsq_part_groups_per_lane(n) groups per lane -- a function of n only, so a 16-bit call
+// writes the records of the fp32 call on the widened tensors.
+template <typename T>
+int lsq_bwd_part(const T *g, const T *x, T *gx, int64_t n, int act, const double *scale_dev,
+                 double scale_host, const double *zp_dev, double zp_host, int zp_learn, int qmin, int qmax,
+                 double *records, int64_t records_len, void *stream) {
+  if (n <= 0 || !g || !x || !gx || !records || qmin > qmax || !act_ok(act))
+    return VSIQ_E_ARG;
+  const bool vec = (n % 4 == 0) && aligned_vec<T>(g) && aligned_vec<T>(x) && aligned_vec<T>(gx);
+  const int64_t grid = lsq_grid(cdiv(n, 4), lsq_part_groups_per_lane(n));
+  if (grid > 0x7fffffffLL) return VSIQ_E_ARG;
+  if (records_len < 2 * grid) return VSIQ_E_WS;
+  if (zp_learn < 0 || zp_learn > 1) return VSIQ_E_ARG;   // the deferred fold knows modes 0 / 1 only
+  QPSrc src{nullptr, scale_dev, zp_dev, scale_host, zp_host, (float)qmin, (float)qmax, zp_learn, 0};
+  const bool nt = g_tune.nontemporal != 0;
+  launch_lsq(act, vec, nt, g, x, gx, n, src, zp_learn, 0.0, nullptr, records, nullptr, grid, (hipStream_t)stream);
+  return launch_rc();
+}
+
 #define VSIQ_LSQ_BWD_INST(T)                                                                                  \
   template int lsq_bwd<T>(const T *, const T *, T *, int64_t, int, const double *, double, const double *, \
                           double, int, int, int, double, double *, double *, int64_t, uint32_t *, void *)
+#define VSIQ_LSQ_BWD_PART_INST(T)                                                                              \
+  template int lsq_bwd_part<T>(const T *, const T *, T *, int64_t, int, const double *, double, const double *, \
+                               double, int, int, int, double *, int64_t, void *)
 extern VSIQ_LSQ_BWD_INST(bf16_t);
 extern VSIQ_LSQ_BWD_INST(f16_t);
+extern VSIQ_LSQ_BWD_PART_INST(bf16_t);
+extern VSIQ_LSQ_BWD_PART_INST(f16_t);
 
 }  // namespace vsiq

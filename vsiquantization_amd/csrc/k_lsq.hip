@@ -14,21 +14,12 @@ int lsq_bwd(const float *g, const float *x, float *gx, int64_t n, int act, const
                         grad_out, ws, ws_len, counter, stream);
 }
 
-// Records-only K4 (PART): same grid, per-element code and block records as lsq_bwd.
+// the fp32 records-only K4 (PART) by its plain name
 int lsq_bwd_part(const float *g, const float *x, float *gx, int64_t n, int act, const double *scale_dev,
                  double scale_host, const double *zp_dev, double zp_host, int zp_learn, int qmin, int qmax,
                  double *records, int64_t records_len, void *stream) {
-  if (n <= 0 || !g || !x || !gx || !records || qmin > qmax || !act_ok(act))
-    return VSIQ_E_ARG;
-  const bool vec = (n % 4 == 0) && aligned16(g) && aligned16(x) && aligned16(gx);
-  const int64_t grid = lsq_grid(cdiv(n, 4), lsq_part_groups_per_lane(n));
-  if (grid > 0x7fffffffLL) return VSIQ_E_ARG;
-  if (records_len < 2 * grid) return VSIQ_E_WS;
-  if (zp_learn < 0 || zp_learn > 1) return VSIQ_E_ARG;   // the deferred fold knows modes 0 / 1 only
-  QPSrc src{nullptr, scale_dev, zp_dev, scale_host, zp_host, (float)qmin, (float)qmax, zp_learn, 0};
-  const bool nt = g_tune.nontemporal != 0;
-  launch_lsq(act, vec, nt, g, x, gx, n, src, zp_learn, 0.0, nullptr, records, nullptr, grid, (hipStream_t)stream);
-  return launch_rc();
+  return lsq_bwd_part<float>(g, x, gx, n, act, scale_dev, scale_host, zp_dev, zp_host, zp_learn, qmin, qmax,
+                             records, records_len, stream);
 }
 
 // ----------------------------------------------------------------------------
@@ -593,6 +584,19 @@ int vsiq_act_lsq_bwd_part_f32(const float *g, const float *c, float *gc, int64_t
                               void *stream) {
   return lsq_bwd_part(g, c, gc, n, act, scale_dev, scale_host, zp_dev, zp_host, zp_learn, qmin, qmax, records,
                       records_len, stream);
+}
+
+int vsiq_act_lsq_bwd_part_t(const void *g, const void *c, void *gc, int64_t n, int dtype, int act,
+                            const double *scale_dev, double scale_host, const double *zp_dev, double zp_host,
+                            int zp_learn, int qmin, int qmax, double *records, int64_t records_len,
+                            void *stream) {
+  if (!dtype_ok(dtype)) return VSIQ_E_ARG;
+  if (n == 0) return 0;
+  return with_dtype(dtype, [&](auto D) {
+    using T = typename decltype(D)::type;
+    return lsq_bwd_part<T>((const T *)g, (const T *)c, (T *)gc, n, act, scale_dev, scale_host, zp_dev, zp_host,
+                           zp_learn, qmin, qmax, records, records_len, stream);
+  });
 }
 
 int vsiq_lsq_fold_multi(const vsiq_lsq_fold *folds, int count, void *stream) {

@@ -7,8 +7,9 @@ point) gradient right away (autograd of uniform.py:47-56).  On MI355X that gradi
 device-wide reduction: K4 ends every launch with a record drain, arrival atomics and a
 last-workgroup fold, 3-5 us per launch at 2-26M elements (C4's 27 activation quantizers:
 ~135 us of a 1.28 ms backward).  Nothing reads those gradients before the optimizer,
-so this mode runs each quantizer's backward records-only (vsiq_act_lsq_bwd_part_f32:
-grad_x bit-identical, one record per workgroup, no reduction) and folds every
+so this mode runs each quantizer's backward records-only (vsiq_act_lsq_bwd_part_f32, or
+vsiq_act_lsq_bwd_part_t on the bf16 / fp16 tensors of an autocast model: grad_x
+bit-identical, one record per workgroup, no reduction) and folds every
 quantizer's records in ONE launch (vsiq_lsq_fold_multi) when autograd reaches a bundle
 node that sits between the model's f64 ``scale`` / ``zero_point`` Parameters and their
 uses.  The bundle's backward runs once all of its uses have delivered their (record)
@@ -53,16 +54,19 @@ class _Fold:
 
 
 def lsq_backward_part(g, x, scale, zero_point, qmin, qmax, learn_zp, act, records):
-    """K4 records-only: grad_x; the call's per-workgroup {sum t, sum z} into ``records``."""
-    g = H.require_device_f32(g, "grad_output")
+    """K4 records-only: grad_x; the call's per-workgroup {sum t, sum z} into ``records``.
+    bfloat16 / float16 g and x (the same dtype): grad_x is the fp32 call's on the widened
+    tensors rounded once to that dtype, the records are the fp32 call's bit for bit."""
+    g, dt = H.require_device_float(g, "grad_output")
+    x = H.require_same_dtype(x, g, "x")
     dev = g.device
     gx = torch.empty_like(g)
     sd, sh = scalar_source(scale, dev)
     zd, zh = scalar_source(zero_point, dev)
-    rc = H.lib().vsiq_act_lsq_bwd_part_f32(H.ptr(g), H.ptr(x), H.ptr(gx), H.c_i64(g.numel()), H.act_code(act),
-                                           H.ptr(sd), sh, H.ptr(zd), zh, int(bool(learn_zp)), int(qmin), int(qmax),
-                                           H.ptr(records), H.c_i64(records.numel()), H.stream_of(dev))
-    H.check(rc, "vsiq_act_lsq_bwd_part_f32")
+    rc = H.lib().vsiq_act_lsq_bwd_part_t(H.ptr(g), H.ptr(x), H.ptr(gx), H.c_i64(g.numel()), dt, H.act_code(act),
+                                         H.ptr(sd), sh, H.ptr(zd), zh, int(bool(learn_zp)), int(qmin), int(qmax),
+                                         H.ptr(records), H.c_i64(records.numel()), H.stream_of(dev))
+    H.check(rc, "vsiq_act_lsq_bwd_part_t")
     return gx, zd, zh
 
 
@@ -81,11 +85,12 @@ def fold(entries) -> None:
 class DeferredLearnFn(torch.autograd.Function):
     """FakeQuantLearnFn with the records-only backward: the qparam gradients it returns
     are placeholders (views of a pending f64[2]) that the bundle folds.  The Python form
-    of the C++ node fq_learn_deferred (VSIQ_TORCH_EXT=0; tests compare the two)."""
+    of the C++ node fq_learn_deferred (VSIQ_TORCH_EXT=0; tests compare the two), and the
+    only form for bfloat16 / float16 tensors."""
 
     @staticmethod
     def forward(ctx, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act):
-        x = H.require_device_f32(x)
+        x, _ = H.require_device_float(x)
         y, _, _ = fake_quant(x, scale, zero_point, qmin, qmax, zp_round=learn_zp, act=act)
         ctx.save_for_backward(x)
         ctx.scale, ctx.zp = scale, zero_point
@@ -97,6 +102,8 @@ class DeferredLearnFn(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         qmin, qmax, gscale, learn_zp, act = ctx.args
         s, z = ctx.scale, ctx.zp
+        if gy.dtype != x.dtype:
+            raise TypeError(f"grad_output is {gy.dtype}, the fake-quantized tensor was {x.dtype}")
         dev = x.device
         e = _Fold()
         e.nrec = int(H.lib().vsiq_lsq_part_records(H.c_i64(x.numel())))
@@ -117,8 +124,10 @@ class DeferredLearnFn(torch.autograd.Function):
 def deferred_learn(x, scale, zero_point, qmin, qmax, gscale, learn_zp, act):
     """Learnable fake quant whose backward is records-only (K4d): the C++ node of
     _vsiq_torch.so (FqLearnDeferredBackward, no Python in the backward), or
-    DeferredLearnFn with VSIQ_TORCH_EXT=0."""
-    if H.torch_ext_enabled():
+    DeferredLearnFn with VSIQ_TORCH_EXT=0 and for bfloat16 / float16 tensors (the C++
+    node is fp32-only, like fq_learn)."""
+    half = isinstance(x, torch.Tensor) and x.dtype in (torch.bfloat16, torch.float16)
+    if H.torch_ext_enabled() and not half:
         x = H.require_device_f32(x)
         cuda_z = isinstance(zero_point, torch.Tensor) and zero_point.device.type == "cuda"
         zt = zero_point if cuda_z else None   # a CPU tensor / number: its host value (scalar_source)

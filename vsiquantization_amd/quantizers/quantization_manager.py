@@ -438,8 +438,7 @@ class QuantizationManager(nn.Module):
                 from .deferred import deferred_learn
                 q = self.quantizer
                 gscale, zp, learn_zp = q.learn_args(x, d[1])
-                # (bfloat16 / float16 tensors: K4d is fp32-only, they take the per-call K4 below)
-                if not isinstance(gscale, torch.Tensor) and learn_zp != 2 and x.dtype == torch.float32:
+                if not isinstance(gscale, torch.Tensor) and learn_zp != 2:
                     return deferred_learn(x, d[0], zp, q.qmin, q.qmax, gscale, learn_zp, act)
             if act is None:
                 return self.quantizer.quantize(x, self.scale, self.zero_point, True)
