@@ -536,6 +536,30 @@ int vsiq_act_fq_fwd_f32(const float *c, float *y, void *codes, uint64_t *mask, i
 int vsiq_act_observe_f32(const float *c, int64_t n, int act, double *stats_out, float *run_minmax,
                          double *qp_out, int symmetric, double qden, double eps, double *ws,
                          int64_t ws_len, uint32_t *counter, void *stream);
+/*
+ * The percentile observer's second pass (PercentileObserver; added within ABI 13: purely
+ * additive, no existing entry changes).  After vsiq_act_observe_f32 on the same (c, n, act)
+ * with run_minmax and qp_out NULL has written `stats`, this call clips that call's range
+ * to a percentile of its values and applies the running update and f64 qparams of
+ * vsiq_act_observe_f32 to the clipped range (lo, hi), also written to clip_out f64[2].
+ * With N = n, B = bins, t = tail = (100 - percentile) / 100, mn / mx the record's fp32
+ * min / max, all in f64 and never contracted:
+ *   bin(v) = min(B - 1, (int64)((v - mn) * (B / (mx - mn)))),  K = floor(N * t)
+ *   bl = smallest b with h[0] + ... + h[b] > K,  bh = largest b with h[b] + ... + h[B-1] > K
+ *   lo = bl == 0     ? mn : max(mn, (float)(mn + bl * ((mx - mn) / B)))
+ *   hi = bh == B - 1 ? mx : min(mx, (float)(mn + (bh + 1) * ((mx - mn) / B)))
+ * The call is MinMaxObserver's ((lo, hi) = (mn, mx), no histogram) when the record counts
+ * a NaN, mn == mx, mn or mx is not finite, or tail == 0.  Counts are integers: the result
+ * does not depend on the order of the atomics.  `stats` is read on the device (no sync);
+ * `hist` is uint64[hist_len >= bins], all 0 before the first call and left all 0, like
+ * `counter`.  bins: a power of two in [256, 4096]; tail in [0, 0.5); else VSIQ_E_ARG, as
+ * for nulls (run_minmax and qp_out may be NULL) and n <= 0; hist_len < bins: VSIQ_E_WS.
+ * fp32 only.
+ */
+int vsiq_act_observe_hist_f32(const float *c, int64_t n, int act, const double *stats, int bins, double tail,
+                              uint64_t *hist, int64_t hist_len, uint32_t *counter, float *run_minmax,
+                              double *qp_out, double *clip_out, int symmetric, double qden, double eps,
+                              void *stream);
 int vsiq_act_ste_bwd_f32(const float *g, const uint64_t *mask, const float *c, float *gc, int64_t n,
                          int act, const double *scale_dev, int64_t rowlen, double scale_host,
                          void *stream);
@@ -672,9 +696,14 @@ int vsiq_bn_fold_f32(const float *w, const float *b, const float *gamma, const f
  *   vsiq_host_fq_fwd_f32   = vsiq_act_fq_fwd_f32         (uniform.py:55,95; qp nullable)
  *   vsiq_host_ste_bwd_f32  = vsiq_act_ste_bwd_f32        (autograd of uniform.py:55,95)
  *   vsiq_host_lsq_bwd_f32  = vsiq_act_lsq_bwd_f32        (autograd of uniform.py:47-56)
+ *   vsiq_host_observe_hist_f32 = vsiq_act_observe_hist_f32  (no counter; hist a host uint64[bins],
+ *                            all 0 before and after; given the same `stats`, the device's bits)
  */
 int vsiq_host_observe_f32(const float *x, int64_t n, int act, double *stats_out, float *run_minmax, double *qp_out,
                           int symmetric, double qden, double eps);
+int vsiq_host_observe_hist_f32(const float *x, int64_t n, int act, const double *stats, int bins, double tail,
+                               uint64_t *hist, int64_t hist_len, float *run_minmax, double *qp_out,
+                               double *clip_out, int symmetric, double qden, double eps);
 int vsiq_host_fq_fwd_f32(const float *x, float *y, uint8_t *codes, uint8_t *mask, int64_t n, int act,
                          const double *qp, double scale, double zp, int zp_round, int discrete, int qmin,
                          int qmax);

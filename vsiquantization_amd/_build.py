@@ -46,7 +46,8 @@ FLAGS = [
 # of v_pk_add_f32 fed by v_and / v_mov pairs -- C5's K2m 175 -> 168 us on MI355X (C2 / C3
 # / C4 kernels measured unchanged with it, so they keep the default).  k_observe_fq.hip
 # and k_lib.hip were one translation unit with it: their kernels keep the flag they were
-# built with.
+# built with.  k_observe_hist.hip (the percentile observer's histogram pass; picked up by
+# sources() like every csrc/*.hip) has no fp32 |x| sums to keep scalar: default flags.
 _NO_SLP = ["-fno-slp-vectorize"]
 FILE_FLAGS = {"k_observe.hip": _NO_SLP, "k_observe_half.hip": _NO_SLP, "k_observe_fq.hip": _NO_SLP,
               "k_lib.hip": _NO_SLP}

@@ -36,6 +36,7 @@ PART_LEN = 8   # VSIQ_PART_LEN: doubles per K2p partial record
 PART_MAX_RECORDS = 4096   # VSIQ_PART_MAX_RECORDS
 QP_SCALE, QP_ZP, QP_MIN, QP_MAX = range(4)
 QP_LEN = 4
+HIST_MIN_BINS, HIST_MAX_BINS = 256, 4096   # vsiq_act_observe_hist_f32: bins, a power of two in between
 TUNE_NONTEMPORAL, TUNE_STORE_DEFER = 2, 6
 TUNE_OBS_KERNEL, TUNE_LSQ_GROUPS, TUNE_PC_PACKED = 7, 9, 10
 TUNE_STORE_GATE = 11
@@ -199,6 +200,8 @@ _SIGS = {
                              c_int, c_int, c_p], c_int),
     "vsiq_act_observe_f32": ([c_p, c_i64, c_int, c_p, c_p, c_p, c_int, c_d, c_d, c_p, c_i64, c_p, c_p],
                              c_int),
+    "vsiq_act_observe_hist_f32": ([c_p, c_i64, c_int, c_p, c_int, c_d, c_p, c_i64, c_p, c_p, c_p, c_p, c_int, c_d,
+                                   c_d, c_p], c_int),
     "vsiq_observe_part_records": ([c_i64], c_i64),
     "vsiq_observe_part_out_records": ([c_i64], c_i64),
     "vsiq_act_observe_part_f32": ([c_p, c_i64, c_int, c_p, c_i64, c_p], c_int),
@@ -221,6 +224,8 @@ _SIGS = {
     "vsiq_lsq_fwd_multi_f32": ([c_p, c_int, c_p], c_int),
     "vsiq_lsq_bwd_multi_f32": ([c_p, c_int, c_p, c_i64, c_p, c_p], c_int),
     "vsiq_host_observe_f32": ([c_p, c_i64, c_int, c_p, c_p, c_p, c_int, c_d, c_d], c_int),
+    "vsiq_host_observe_hist_f32": ([c_p, c_i64, c_int, c_p, c_int, c_d, c_p, c_i64, c_p, c_p, c_p, c_int, c_d, c_d],
+                                   c_int),
     "vsiq_host_fq_fwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_int, c_p, c_d, c_d, c_int, c_int, c_int, c_int], c_int),
     "vsiq_host_ste_bwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_int, c_d], c_int),
     "vsiq_host_lsq_bwd_f32": ([c_p, c_p, c_p, c_i64, c_int, c_d, c_d, c_int, c_int, c_int, c_d, c_p], c_int),
@@ -506,6 +511,14 @@ class _Workspace:
         if c is None or c.numel() < channels:
             c = self._chan = torch.zeros(max(channels, 256), dtype=torch.int32, device=self.device)
         return c
+
+    def histogram(self) -> torch.Tensor:
+        """The percentile observer's global histogram, uint64[HIST_MAX_BINS] as int64 (zeroed
+        once; every launch leaves it zero)."""
+        h = getattr(self, "_hist", None)
+        if h is None:
+            h = self._hist = torch.zeros(HIST_MAX_BINS, dtype=torch.int64, device=self.device)
+        return h
 
 
 _WS = {}

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "host_simd.h"
+#include "k_observe_hist.cuh"
 #include "mean_cascade.cuh"
 #include "vsiq_common.cuh"
 
@@ -371,6 +372,46 @@ int vsiq_host_observe_f32(const float *x, int64_t n, int act, double *stats_out,
   }
   if (stats_out) write_stats(stats_out, f, n);
   observer_update((float)f[0], (float)f[1], f[2] > 0.0, run_minmax, qp_out, symmetric, qden, eps);
+  return 0;
+}
+
+// The percentile observer's second pass on the host (k_observe_hist.hip's, with its
+// arithmetic: k_observe_hist.cuh): each chunk counts into a histogram of its own and adds
+// its non-empty bins to `hist` (integer counts: any thread count, any order, the same
+// result); `hist` is all zero before and after, like the device buffer.
+int vsiq_host_observe_hist_f32(const float *x, int64_t n, int act, const double *stats, int bins, double tail,
+                               uint64_t *hist, int64_t hist_len, float *run_minmax, double *qp_out,
+                               double *clip_out, int symmetric, double qden, double eps) {
+  if (n <= 0 || !x || !stats || !hist || !clip_out || !act_ok(act)) return VSIQ_E_ARG;
+  if (!hist_bins_ok(bins) || !hist_tail_ok(tail)) return VSIQ_E_ARG;
+  if (hist_len < bins) return VSIQ_E_WS;
+  const float mn = (float)stats[VSIQ_ST_MIN], mx = (float)stats[VSIQ_ST_MAX];
+  const bool has_nan = stats[VSIQ_ST_NAN] > 0.0;
+  if (hist_noclip(mn, mx, has_nan, tail)) {
+    hist_finish(mn, mx, has_nan, run_minmax, qp_out, clip_out, symmetric, qden, eps);
+    return 0;
+  }
+  const int kind = act_kind(act);
+  const SiluLay L = act_lay(act, n);
+  const HistMap m = hist_map(mn, mx, bins);
+  for_chunks(n, [&](int64_t, int64_t b, int64_t e) {
+    std::vector<uint32_t> h((size_t)bins);
+    for (int64_t i = b; i < e; ++i) ++h[(size_t)hist_bin(act_at(x[i], kind, i, L), m)];
+    for (int k = 0; k < bins; ++k)
+      if (h[(size_t)k]) __atomic_fetch_add(&hist[k], (uint64_t)h[(size_t)k], __ATOMIC_RELAXED);
+  });
+  const uint64_t K = hist_rank(n, tail);
+  int bl = 0, bh = bins - 1;
+  uint64_t p = 0;
+  for (int k = 0; k < bins; ++k)
+    if ((p += hist[k]) > K) { bl = k; break; }
+  p = 0;
+  for (int k = bins - 1; k >= 0; --k)
+    if ((p += hist[k]) > K) { bh = k; break; }
+  std::memset(hist, 0, (size_t)bins * sizeof(uint64_t));
+  float lo, hi;
+  hist_clip(mn, mx, bins, bl, bh, &lo, &hi);
+  hist_finish(lo, hi, false, run_minmax, qp_out, clip_out, symmetric, qden, eps);
   return 0;
 }
 

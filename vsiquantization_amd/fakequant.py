@@ -442,6 +442,47 @@ def observe_tensor(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, eps: 
     return qp, st
 
 
+def percentile_tail(percentile) -> float:
+    """t = (100 - percentile) / 100 as a Python float: the fraction of a call's elements each
+    end of its range may lose (0 <= t < 0.5, else ValueError)."""
+    t = (100.0 - percentile) / 100.0
+    if not 0.0 <= t < 0.5:
+        raise ValueError(f"percentile must be in (50, 100], got {percentile!r}")
+    return t
+
+
+def observe_percentile(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, eps: float = 1e-8,
+                       run_minmax: torch.Tensor | None = None, tail: float, bins: int = 2048, act=None):
+    """observe_tensor with the call's range clipped to a percentile of its values before the
+    running update (PercentileObserver): K2 for the stats record (of the unclipped tensor),
+    then the histogram pass, which reads that record on the device (no sync), drops up to
+    floor(N * tail) elements' worth of bins at each end and applies the running update and
+    f64 qparams to the clipped range.  Returns (qp f64[QP_LEN], stats f64[ST_LEN], clip
+    f64[2] = (lo, hi)).  fp32 only; CPU tensors: the native host loop (host.py)."""
+    tail = float(tail)
+    if not 0.0 <= tail < 0.5:
+        raise ValueError(f"tail must be in [0, 0.5), got {tail!r}")
+    if bins & (bins - 1) or not H.HIST_MIN_BINS <= bins <= H.HIST_MAX_BINS:
+        raise ValueError(f"bins must be a power of two in [{H.HIST_MIN_BINS}, {H.HIST_MAX_BINS}], got {bins!r}")
+    if _host.is_host(x):
+        return _host.observe_percentile(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=run_minmax,
+                                        tail=tail, bins=bins, act=act)
+    x = H.require_device_f32(x)
+    _, st = observe_tensor(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=None, want_qp=False,
+                           act=act)
+    dev = x.device
+    qp = torch.empty(H.QP_LEN, dtype=torch.float64, device=dev)
+    clip = torch.empty(2, dtype=torch.float64, device=dev)
+    w = H.workspace(dev, x.numel())
+    hist = w.histogram()
+    rc = H.lib().vsiq_act_observe_hist_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), H.ptr(st), int(bins), tail,
+                                           H.ptr(hist), _i64(hist.numel()), H.ptr(w.counter), H.ptr(run_minmax),
+                                           H.ptr(qp), H.ptr(clip), int(bool(symmetric)),
+                                           qden(symmetric, num_bits, eps), float(eps), H.stream_of(dev))
+    H.check(rc, "vsiq_act_observe_hist_f32")
+    return qp, st, clip
+
+
 # K8 (one workgroup holds the tensor) up to here; K9 above: through the API K8 is
 # 10.9-12.1 us against 17.9-18.2 us for K2 + K1 at 432-16384 elements, but its GPU time
 # grows past K2 + K1's ~9 us above ~16K elements (65536: 16.2 us).

@@ -146,6 +146,26 @@ def observe_tensor(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, want_
     return qp, st
 
 
+def observe_percentile(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, tail, bins=2048, act=None):
+    """Host counterpart of fakequant.observe_percentile: the host observer pass for the
+    stats record, then the host histogram loop -> (qp, stats, clip f64[2])."""
+    from .fakequant import qden
+    _, st = observe_tensor(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=None, want_qp=False,
+                           act=act)
+    x = _f32(x)
+    if run_minmax is not None and (run_minmax.device.type != "cpu" or run_minmax.dtype != torch.float32):
+        raise ValueError("host observe: the running state must be a CPU float32 tensor")
+    qp = torch.empty(H.QP_LEN, dtype=torch.float64)
+    clip = torch.empty(2, dtype=torch.float64)
+    hist = torch.zeros(int(bins), dtype=torch.int64)
+    rc = H.lib().vsiq_host_observe_hist_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), H.ptr(st), int(bins),
+                                            float(tail), H.ptr(hist), _i64(hist.numel()), H.ptr(run_minmax),
+                                            H.ptr(qp), H.ptr(clip), int(bool(symmetric)),
+                                            qden(symmetric, num_bits, eps), float(eps))
+    H.check(rc, "vsiq_host_observe_hist_f32")
+    return qp, st, clip
+
+
 # --------------------------------------------------------------------------- per-channel
 def _rows(x):
     C = x.shape[0] if x.dim() > 0 else 1
@@ -318,5 +338,6 @@ def simd() -> bool:
     return bool(H.lib().vsiq_host_simd())
 
 
-__all__ = ["is_host", "fake_quant", "fake_quant_fixed", "fake_quant_learn", "observe_tensor", "pc_observe_fq",
+__all__ = ["is_host", "fake_quant", "fake_quant_fixed", "fake_quant_learn", "observe_tensor", "observe_percentile",
+           "pc_observe_fq",
            "pc_fake_quant", "threads", "simd"]

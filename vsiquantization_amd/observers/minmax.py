@@ -40,6 +40,9 @@ class MinMaxObserver(BaseObserver):
     # weakref to the QuantizationManager whose deferred calibration calls (not folded yet)
     # hold this observer's later updates: any read or update folds them first
     _defer_owner = None
+    # one K2 pass per call whose record alone decides the update: what QuantizationManager's
+    # fused and deferred paths (K8 / K9, K2o, K2p / K2m, the multi-GPU exchange) rely on
+    single_pass = True
 
     def __init__(self, symmetric=True, num_bits=8, eps=1e-8):
         self.symmetric = symmetric

@@ -308,8 +308,12 @@ class QuantizationManager(nn.Module):
             rs = self.observer.observe(x, want_row_stats=True)
             self._record_stats(stats_from_row_sums(rs, x.numel()), x)
             self.scale, self.zero_point = self.observer.get_scale_zero_point()
-        elif self.dist_group is not None or self.dist_defer:
+        elif (self.dist_group is not None or self.dist_defer) and self.observer.single_pass:
             self._collect_distributed(x, act)
+        elif self.dist_group is not None:
+            # a two-pass observer's second pass needs the whole batch's range first
+            raise NotImplementedError(f"{type(self.observer).__name__} does not support a multi-GPU dist_group: "
+                                      "its second pass needs every rank's range; calibrate it on one GPU")
         else:
             qp, st = self.observer.observe_device(x, act=act)
             self._record_stats(st[H.ST_MEANABS:H.ST_STD + 1], x, act)
@@ -444,7 +448,7 @@ class QuantizationManager(nn.Module):
                 return self.quantizer.quantize(x, self.scale, self.zero_point, True)
             return self.quantizer.quantize(x, self.scale, self.zero_point, True, act=act)
         if (act is not None and not self.is_quantize and self.dist_defer and not self.is_learning_scale
-                and self.is_observer_qparam and self._act_fusable(x)
+                and self.is_observer_qparam and self._act_fusable(x) and self.observer.single_pass
                 and not (x.requires_grad and torch.is_grad_enabled())):
             return self._observe_deferred_act(x, act)
         if act is not None and not (self.is_quantize and self._act_fusable(x)):
@@ -498,6 +502,7 @@ class QuantizationManager(nn.Module):
         if not (self.dist_group is not None and not self.dist_defer and self.is_quantize
                 and not self.is_learning_scale and self.is_observer_qparam
                 and type(self.quantizer) is UniformQuantizer and isinstance(obs, MinMaxObserver)
+                and obs.single_pass
                 and not isinstance(obs, PerChannelMinMaxObserver) and self._device_observer(x)
                 and x.dtype == torch.float32 and x.numel() > 0):
             return None
@@ -528,6 +533,7 @@ class QuantizationManager(nn.Module):
         obs = self.observer
         if not (self.is_quantize and not self.is_learning_scale and self.is_observer_qparam
                 and type(self.quantizer) is UniformQuantizer and isinstance(obs, MinMaxObserver)
+                and obs.single_pass
                 and not isinstance(obs, PerChannelMinMaxObserver) and self._device_observer(x)
                 and self.dist_group is None and not self.dist_defer and x.dtype == torch.float32
                 and 0 < x.numel() <= min(_OBSERVE_FQ_MAX, observe_fq_parts_max_elems())):
