@@ -560,6 +560,43 @@ int vsiq_act_observe_hist_f32(const float *c, int64_t n, int act, const double *
                               uint64_t *hist, int64_t hist_len, uint32_t *counter, float *run_minmax,
                               double *qp_out, double *clip_out, int symmetric, double qden, double eps,
                               void *stream);
+/*
+ * The MSE observer's second pass (MSEObserver; added within ABI 13: purely additive, no
+ * existing entry changes).  After vsiq_act_observe_f32 on the same (c, n, act) with
+ * run_minmax and qp_out NULL has written `stats`, this call shrinks that call's range by
+ * the ratio whose qparams fake-quantize the tensor with the smallest summed squared error
+ * and applies the running update and f64 qparams of vsiq_act_observe_f32 to that range.
+ * With mn / mx the record's fp32 min / max, v_i = act(c_i) as vsiq_act_fq_fwd_f32 computes
+ * it, r[0..K-1] = ratios (HOST f64[count], K = count in [1, 128], r[0] == 1.0, every r[k]
+ * in (0, 1]) and (qmin, qmax) the integer grid; all in f64 and never contracted:
+ *   lo_k = (float)((double)mn * r[k]),  hi_k = (float)((double)mx * r[k])
+ *   (s_k, z_k) = the qparams vsiq_act_observe_f32 returns from the running state
+ *                (min(lo_k, 0), max(hi_k, 0)) for (symmetric, qden, eps);
+ *                s32 = (float)s_k, z32 = (float)z_k
+ *   candidate k is valid iff s32 is finite and > 0 and z_k is finite
+ *   y_i  = the output of vsiq_act_fq_fwd_f32 for (v_i, s32, z32, qmin, qmax), bit for bit
+ *   E_k  = sum_i ((double)y_i - (double)v_i)^2   (each term: one f64 subtraction, one f64
+ *          multiplication);  E_k = +inf for an invalid candidate
+ *   k*   = the smallest k with E_k minimal (a strict < scan from k = 0)
+ *   (lo, hi) = (lo_k*, hi_k*) -> running update and qparams; clip_out f64[2] = (lo, hi),
+ *   err_out f64[count] = every E_k, pick_out int32[1] = k*.
+ * The terms are fixed by this definition; the order of the f64 sum is the implementation's:
+ * the device adds in an order fixed per (n, count) (per-workgroup records in fixed slots of
+ * `ws`, added in workgroup order by the last workgroup to arrive; no floating-point
+ * atomics), so it returns the same bits run to run; exact ties go to the smaller k.
+ * The call is MinMaxObserver's ((lo, hi) = (mn, mx), k* = 0, err_out all +inf, no pass over
+ * the tensor) when the record counts a NaN, mn == mx, mn or mx is not finite, or count == 1.
+ * `stats` is read on the device (no sync); the ratios travel by value with the launch (the
+ * call captures into a HIP graph); `ws` is f64[ws_len >= vsiq_observe_mse_ws_doubles(n,
+ * count)]; `counter` is left all 0.  VSIQ_E_ARG: a null (run_minmax and qp_out may be
+ * NULL), n <= 0, a bad act, count outside [1, 128], ratios[0] != 1, a ratio outside (0, 1]
+ * or NaN, qmin >= qmax; VSIQ_E_WS: ws_len too small.  fp32 only.
+ */
+int vsiq_act_observe_mse_f32(const float *c, int64_t n, int act, const double *stats, const double *ratios,
+                             int count, int qmin, int qmax, double *ws, int64_t ws_len, uint32_t *counter,
+                             float *run_minmax, double *qp_out, double *clip_out, double *err_out,
+                             int32_t *pick_out, int symmetric, double qden, double eps, void *stream);
+int64_t vsiq_observe_mse_ws_doubles(int64_t n, int count);
 int vsiq_act_ste_bwd_f32(const float *g, const uint64_t *mask, const float *c, float *gc, int64_t n,
                          int act, const double *scale_dev, int64_t rowlen, double scale_host,
                          void *stream);
@@ -698,12 +735,19 @@ int vsiq_bn_fold_f32(const float *w, const float *b, const float *gamma, const f
  *   vsiq_host_lsq_bwd_f32  = vsiq_act_lsq_bwd_f32        (autograd of uniform.py:47-56)
  *   vsiq_host_observe_hist_f32 = vsiq_act_observe_hist_f32  (no counter; hist a host uint64[bins],
  *                            all 0 before and after; given the same `stats`, the device's bits)
+ *   vsiq_host_observe_mse_f32 = vsiq_act_observe_mse_f32  (no workspace, no counter; the sums
+ *                            add 64K-element chunks in chunk order: given the same `stats`, the
+ *                            device's E_k up to that order, hence its pick, range, state and qparams
+ *                            wherever the two smallest E_k are not within rounding of each other)
  */
 int vsiq_host_observe_f32(const float *x, int64_t n, int act, double *stats_out, float *run_minmax, double *qp_out,
                           int symmetric, double qden, double eps);
 int vsiq_host_observe_hist_f32(const float *x, int64_t n, int act, const double *stats, int bins, double tail,
                                uint64_t *hist, int64_t hist_len, float *run_minmax, double *qp_out,
                                double *clip_out, int symmetric, double qden, double eps);
+int vsiq_host_observe_mse_f32(const float *x, int64_t n, int act, const double *stats, const double *ratios,
+                              int count, int qmin, int qmax, float *run_minmax, double *qp_out, double *clip_out,
+                              double *err_out, int32_t *pick_out, int symmetric, double qden, double eps);
 int vsiq_host_fq_fwd_f32(const float *x, float *y, uint8_t *codes, uint8_t *mask, int64_t n, int act,
                          const double *qp, double scale, double zp, int zp_round, int discrete, int qmin,
                          int qmax);

@@ -7,6 +7,7 @@ Importing the package registers the quantizer/observer classes by name in
   UniformQuantizer, MinMaxObserver                  (reference names, same behaviour)
   LSQQuantizer, LSQObserver                         (names the reference README advertises)
   PerChannelUniformQuantizer, PerChannelMinMaxObserver  (per-channel, axis 0)
+  PercentileObserver, MSEObserver                   (calibrators that clip the min / max range)
 
 plus ``LSQFakeQuantize`` (quantizers/lsq_module.py, the torch.ao-based LSQ module).
 All fake-quant arithmetic runs in the HIP kernels of ``csrc/`` through the C ABI of
@@ -24,6 +25,8 @@ from .quantizers.per_channel import PerChannelUniformQuantizer  # noqa: F401
 from .observers.minmax import MinMaxObserver  # noqa: F401
 from .observers.minmax import LSQObserver  # noqa: F401
 from .observers.per_channel import PerChannelMinMaxObserver  # noqa: F401
+from .observers.percentile import PercentileObserver  # noqa: F401
+from .observers.mse import MSEObserver  # noqa: F401
 from .quantizers.quantization_manager import QuantizationManager  # noqa: F401
 from .quantizers.fake_quantize import FakeQuantize  # noqa: F401
 from .quantizers.lsq_module import LSQFakeQuantize  # noqa: F401

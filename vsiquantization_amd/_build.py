@@ -47,7 +47,9 @@ FLAGS = [
 # / C4 kernels measured unchanged with it, so they keep the default).  k_observe_fq.hip
 # and k_lib.hip were one translation unit with it: their kernels keep the flag they were
 # built with.  k_observe_hist.hip (the percentile observer's histogram pass; picked up by
-# sources() like every csrc/*.hip) has no fp32 |x| sums to keep scalar: default flags.
+# sources() like every csrc/*.hip) has no fp32 |x| sums to keep scalar: default flags, and
+# k_observe_mse.hip (the MSE observer's error-search pass) is built as it is: like every file
+# never contracted (-ffp-contract=off in FLAGS), which its per-term f64 arithmetic relies on.
 _NO_SLP = ["-fno-slp-vectorize"]
 FILE_FLAGS = {"k_observe.hip": _NO_SLP, "k_observe_half.hip": _NO_SLP, "k_observe_fq.hip": _NO_SLP,
               "k_lib.hip": _NO_SLP}

@@ -37,6 +37,7 @@ PART_MAX_RECORDS = 4096   # VSIQ_PART_MAX_RECORDS
 QP_SCALE, QP_ZP, QP_MIN, QP_MAX = range(4)
 QP_LEN = 4
 HIST_MIN_BINS, HIST_MAX_BINS = 256, 4096   # vsiq_act_observe_hist_f32: bins, a power of two in between
+MSE_MAX_CANDIDATES = 128   # vsiq_act_observe_mse_f32: count in [1, 128]
 TUNE_NONTEMPORAL, TUNE_STORE_DEFER = 2, 6
 TUNE_OBS_KERNEL, TUNE_LSQ_GROUPS, TUNE_PC_PACKED = 7, 9, 10
 TUNE_STORE_GATE = 11
@@ -202,6 +203,9 @@ _SIGS = {
                              c_int),
     "vsiq_act_observe_hist_f32": ([c_p, c_i64, c_int, c_p, c_int, c_d, c_p, c_i64, c_p, c_p, c_p, c_p, c_int, c_d,
                                    c_d, c_p], c_int),
+    "vsiq_act_observe_mse_f32": ([c_p, c_i64, c_int, c_p, c_p, c_int, c_int, c_int, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
+                                  c_p, c_int, c_d, c_d, c_p], c_int),
+    "vsiq_observe_mse_ws_doubles": ([c_i64, c_int], c_i64),
     "vsiq_observe_part_records": ([c_i64], c_i64),
     "vsiq_observe_part_out_records": ([c_i64], c_i64),
     "vsiq_act_observe_part_f32": ([c_p, c_i64, c_int, c_p, c_i64, c_p], c_int),
@@ -226,6 +230,8 @@ _SIGS = {
     "vsiq_host_observe_f32": ([c_p, c_i64, c_int, c_p, c_p, c_p, c_int, c_d, c_d], c_int),
     "vsiq_host_observe_hist_f32": ([c_p, c_i64, c_int, c_p, c_int, c_d, c_p, c_i64, c_p, c_p, c_p, c_int, c_d, c_d],
                                    c_int),
+    "vsiq_host_observe_mse_f32": ([c_p, c_i64, c_int, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_int, c_d,
+                                   c_d], c_int),
     "vsiq_host_fq_fwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_int, c_p, c_d, c_d, c_int, c_int, c_int, c_int], c_int),
     "vsiq_host_ste_bwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_int, c_d], c_int),
     "vsiq_host_lsq_bwd_f32": ([c_p, c_p, c_p, c_i64, c_int, c_d, c_d, c_int, c_int, c_int, c_d, c_p], c_int),

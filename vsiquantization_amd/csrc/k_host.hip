@@ -25,6 +25,7 @@
 
 #include "host_simd.h"
 #include "k_observe_hist.cuh"
+#include "k_observe_mse.cuh"
 #include "mean_cascade.cuh"
 #include "vsiq_common.cuh"
 
@@ -412,6 +413,55 @@ int vsiq_host_observe_hist_f32(const float *x, int64_t n, int act, const double 
   float lo, hi;
   hist_clip(mn, mx, bins, bl, bh, &lo, &hi);
   hist_finish(lo, hi, false, run_minmax, qp_out, clip_out, symmetric, qden, eps);
+  return 0;
+}
+
+// The MSE observer's second pass on the host (k_observe_mse.hip's, with its arithmetic:
+// k_observe_mse.cuh): each chunk sums every candidate's error terms in element order, the
+// chunks' sums are added in chunk order (any thread count, the same result).  y is fq()'s,
+// the element code of vsiq_host_fq_fwd_f32.
+int vsiq_host_observe_mse_f32(const float *x, int64_t n, int act, const double *stats, const double *ratios,
+                              int count, int qmin, int qmax, float *run_minmax, double *qp_out, double *clip_out,
+                              double *err_out, int32_t *pick_out, int symmetric, double qden, double eps) {
+  if (n <= 0 || !x || !stats || !clip_out || !err_out || !pick_out || !act_ok(act)) return VSIQ_E_ARG;
+  if (!mse_ratios_ok(ratios, count) || qmin >= qmax) return VSIQ_E_ARG;
+  const float mn = (float)stats[VSIQ_ST_MIN], mx = (float)stats[VSIQ_ST_MAX];
+  const bool has_nan = stats[VSIQ_ST_NAN] > 0.0;
+  for (int k = 0; k < count; ++k) err_out[k] = __builtin_inf();
+  if (mse_fallback(mn, mx, has_nan, count)) {
+    hist_finish(mn, mx, has_nan, run_minmax, qp_out, clip_out, symmetric, qden, eps);
+    *pick_out = 0;
+    return 0;
+  }
+  const int kind = act_kind(act);
+  const SiluLay L = act_lay(act, n);
+  MseCand cand[kMseMaxCand];
+  for (int k = 0; k < count; ++k) cand[k] = mse_candidate(mn, mx, ratios[k], symmetric, qden, eps);
+  const int64_t nc = cdiv(n, kChunk);
+  std::vector<double> part((size_t)nc * (size_t)count);
+  for_chunks(n, [&](int64_t c, int64_t b, int64_t e) {
+    std::vector<float> v((size_t)(e - b));
+    for (int64_t i = b; i < e; ++i) v[(size_t)(i - b)] = act_at(x[i], kind, i, L);
+    for (int k = 0; k < count; ++k) {
+      if (!cand[k].valid) continue;
+      const HQP p{cand[k].s, cand[k].z, (float)qmin, (float)qmax};
+      double s = 0.0;
+      for (float vi : v) {
+        bool m;
+        uint8_t code;
+        s += mse_term(fq(vi, p, 0, &m, &code), vi);
+      }
+      part[(size_t)c * (size_t)count + (size_t)k] = s;
+    }
+  });
+  for (int k = 0; k < count; ++k) {
+    if (!cand[k].valid) continue;
+    double s = 0.0;
+    for (int64_t c = 0; c < nc; ++c) s += part[(size_t)c * (size_t)count + (size_t)k];   // chunk order
+    err_out[k] = s;
+  }
+  const int pick = mse_pick(err_out, count);
+  mse_finish(mn, mx, ratios[pick], pick, run_minmax, qp_out, clip_out, pick_out, symmetric, qden, eps);
   return 0;
 }
 

@@ -483,6 +483,71 @@ def observe_percentile(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, e
     return qp, st, clip
 
 
+def mse_ratios(candidates: int = 64, min_ratio: float = 2.0 ** -8) -> tuple:
+    """The geometric shrink table of MSEObserver: ``min_ratio ** (k / (candidates - 1))`` in
+    Python floats, k = 0 .. candidates - 1 (so ratios[0] == 1.0 exactly); one candidate: (1.0,)."""
+    candidates = int(candidates)
+    if not 1 <= candidates <= H.MSE_MAX_CANDIDATES:
+        raise ValueError(f"candidates must be in [1, {H.MSE_MAX_CANDIDATES}], got {candidates!r}")
+    min_ratio = float(min_ratio)
+    if not 0.0 < min_ratio <= 1.0:
+        raise ValueError(f"min_ratio must be in (0, 1], got {min_ratio!r}")
+    if candidates == 1:
+        return (1.0,)
+    return tuple(min_ratio ** (k / (candidates - 1)) for k in range(candidates))
+
+
+def check_mse_ratios(ratios) -> tuple:
+    """``ratios`` as a tuple of Python floats, or ValueError: 1 to 128 of them, the first
+    1.0, every one in (0, 1]."""
+    r = tuple(float(v) for v in ratios)
+    if not 1 <= len(r) <= H.MSE_MAX_CANDIDATES:
+        raise ValueError(f"ratios: 1 to {H.MSE_MAX_CANDIDATES} candidates, got {len(r)}")
+    if r[0] != 1.0:
+        raise ValueError(f"ratios[0] must be 1.0 (the min / max range itself), got {r[0]!r}")
+    for v in r:
+        if not 0.0 < v <= 1.0:
+            raise ValueError(f"every ratio must be in (0, 1], got {v!r}")
+    return r
+
+
+def observe_mse(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, eps: float = 1e-8,
+                run_minmax: torch.Tensor | None = None, ratios, qmin: int, qmax: int, act=None):
+    """observe_tensor with the call's range shrunk to the candidate of the smallest
+    quantization error before the running update (MSEObserver): K2 for the stats record (of
+    the whole tensor), then the search pass, which reads that record on the device (no
+    sync), fake-quantizes every element on the grid (qmin, qmax) with the qparams of each
+    range ratios[k] * (min, max), sums the squared errors in f64 and applies the running
+    update and f64 qparams to the range of the smallest sum (include/vsiq.h states the
+    definition).  Returns (qp f64[QP_LEN], stats f64[ST_LEN], clip f64[2] = (lo, hi), err
+    f64[len(ratios)], pick int32[1]).  fp32 only; CPU tensors: the native host loop (host.py)."""
+    r = check_mse_ratios(ratios)
+    qmin, qmax = int(qmin), int(qmax)
+    if qmin >= qmax:
+        raise ValueError(f"qmin must be below qmax, got ({qmin}, {qmax})")
+    if _host.is_host(x):
+        return _host.observe_mse(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=run_minmax,
+                                 ratios=r, qmin=qmin, qmax=qmax, act=act)
+    x = H.require_device_f32(x)
+    _, st = observe_tensor(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=None, want_qp=False,
+                           act=act)
+    dev = x.device
+    qp = torch.empty(H.QP_LEN, dtype=torch.float64, device=dev)
+    clip = torch.empty(2, dtype=torch.float64, device=dev)
+    err = torch.empty(len(r), dtype=torch.float64, device=dev)
+    pick = torch.empty(1, dtype=torch.int32, device=dev)
+    lib = H.lib()
+    w = H.workspace(dev, x.numel())
+    w.reserve_doubles(max(1, int(lib.vsiq_observe_mse_ws_doubles(_i64(x.numel()), len(r)))))
+    table = (H.c_d * len(r))(*r)
+    rc = lib.vsiq_act_observe_mse_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), H.ptr(st), table, len(r), qmin,
+                                      qmax, H.ptr(w.ws), _i64(w.ws_len), H.ptr(w.counter), H.ptr(run_minmax),
+                                      H.ptr(qp), H.ptr(clip), H.ptr(err), H.ptr(pick), int(bool(symmetric)),
+                                      qden(symmetric, num_bits, eps), float(eps), H.stream_of(dev))
+    H.check(rc, "vsiq_act_observe_mse_f32")
+    return qp, st, clip, err, pick
+
+
 # K8 (one workgroup holds the tensor) up to here; K9 above: through the API K8 is
 # 10.9-12.1 us against 17.9-18.2 us for K2 + K1 at 432-16384 elements, but its GPU time
 # grows past K2 + K1's ~9 us above ~16K elements (65536: 16.2 us).

@@ -166,6 +166,29 @@ def observe_percentile(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, t
     return qp, st, clip
 
 
+def observe_mse(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, ratios, qmin, qmax, act=None):
+    """Host counterpart of fakequant.observe_mse (which has validated ``ratios`` and the
+    grid): the host observer pass for the stats record, then the host search loop ->
+    (qp, stats, clip f64[2], err f64[len(ratios)], pick int32[1])."""
+    from .fakequant import qden
+    _, st = observe_tensor(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=None, want_qp=False,
+                           act=act)
+    x = _f32(x)
+    if run_minmax is not None and (run_minmax.device.type != "cpu" or run_minmax.dtype != torch.float32):
+        raise ValueError("host observe: the running state must be a CPU float32 tensor")
+    qp = torch.empty(H.QP_LEN, dtype=torch.float64)
+    clip = torch.empty(2, dtype=torch.float64)
+    err = torch.empty(len(ratios), dtype=torch.float64)
+    pick = torch.empty(1, dtype=torch.int32)
+    table = (H.c_d * len(ratios))(*ratios)
+    rc = H.lib().vsiq_host_observe_mse_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), H.ptr(st), table,
+                                           len(ratios), int(qmin), int(qmax), H.ptr(run_minmax), H.ptr(qp),
+                                           H.ptr(clip), H.ptr(err), H.ptr(pick), int(bool(symmetric)),
+                                           qden(symmetric, num_bits, eps), float(eps))
+    H.check(rc, "vsiq_host_observe_mse_f32")
+    return qp, st, clip, err, pick
+
+
 # --------------------------------------------------------------------------- per-channel
 def _rows(x):
     C = x.shape[0] if x.dim() > 0 else 1
@@ -339,5 +362,5 @@ def simd() -> bool:
 
 
 __all__ = ["is_host", "fake_quant", "fake_quant_fixed", "fake_quant_learn", "observe_tensor", "observe_percentile",
-           "pc_observe_fq",
+           "observe_mse", "pc_observe_fq",
            "pc_fake_quant", "threads", "simd"]

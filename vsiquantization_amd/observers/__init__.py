@@ -2,3 +2,4 @@ from .base import BaseObserver  # noqa: F401
 from .minmax import LSQObserver, MinMaxObserver  # noqa: F401
 from .per_channel import PerChannelMinMaxObserver  # noqa: F401
 from .percentile import PercentileObserver  # noqa: F401
+from .mse import MSEObserver  # noqa: F401

@@ -111,6 +111,10 @@ class QuantizationManager(nn.Module):
         super().__init__()
         self.quantizer = CLASS_REGISTRY[quantizer_name](bits_width, is_symmetric)
         self.observer = CLASS_REGISTRY[observer_name](is_symmetric)
+        if getattr(self.observer, "follows_bits_width", False):
+            # an observer that searches on the quantizer's grid (MSEObserver) takes its width;
+            # every other one keeps the reference's 8-bit observer (qm.py:42)
+            self.observer.num_bits = bits_width
         self.is_learning_scale = is_learning_scale
         self.bits_width = bits_width
         self.scale = 1
