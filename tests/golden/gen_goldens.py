@@ -689,6 +689,129 @@ cases.append(dict(kind="fuse_structure", patterns=patterns, structure=struct,
                            "^0$": dict(bits_w=3, bits_a=3), "fc": dict(bits_w=8, bits_a=6, a_symmetric=False)},
                   state_dict={k: put("toy_" + k, v) for k, v in toy_sd.items()}))
 
+# ---------------------------------------------------------------------------
+# 10. The learnable backward at non-finite, tie and clamp-edge inputs
+#     (tests/lsq_edges_common.py builds the inputs; uniform.py:47-56 and its autograd run
+#     here).  A case with non-finite values pins the CLASS of each gradient (NaN, +inf,
+#     -inf, finite), a finite one its value.  The reference sums in fp32, so its sum could
+#     overflow where the oracle's f64 sum does not: every case asserts that the two give
+#     the same class -- the fixtures and the oracle pin the same thing.
+# ---------------------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(OUT))
+sys.path.append(ROOT)   # after the reference: only `tests` and `oracle` come from here
+from oracle import fakequant_np as NPO  # noqa: E402
+from tests import lsq_edges_common as EC  # noqa: E402
+
+
+def _same_class(ref, orc, what):
+    assert EC.grad_class(ref) == EC.grad_class(orc), f"{what}: reference {ref!r}, oracle {orc!r}"
+
+
+def run_learnable_edges(qc, x, g):
+    q = UniformQuantizer(qc.bits, qc.sym)
+    scale = torch.nn.Parameter(torch.tensor(np.float64(qc.scale)))
+    zp = 0 if qc.learn_zp == 0 else torch.nn.Parameter(torch.tensor(np.float64(qc.zp)))
+    xr = torch.from_numpy(x.copy()).requires_grad_(True)
+    y = q.quantize(xr, scale, zp, True)
+    y.backward(torch.from_numpy(g.copy()))
+    return y.detach(), xr.grad.detach(), float(scale.grad), (float(zp.grad) if qc.learn_zp else None)
+
+
+EDGE_N = 203   # 50 whole groups of four and a tail of three
+edge_idx = 0
+for qi, qc in enumerate(EC.QCASES):
+    # every case: the finite block (values pinned) and everything at once; the first
+    # scale of each zero-point mode and the negative scale also one variant at a time
+    core = qi in (1, 5, 9) or qc.scale == -0.3
+    for variant in (EC.VARIANTS if core else ("finite", "all")):
+        x, g = EC.build_inputs(qc, variant, EDGE_N, seed=1000 + edge_idx)
+        y, gx, gs, gz = run_learnable_edges(qc, x, g)
+        qmin, qmax = EC.qrange(qc)
+        exp = EC.oracle(x, g, qc, NPO.grad_scale(qmax, x.size))
+        key = f"lsqe{edge_idx}"
+        edge_idx += 1
+        _same_class(gs, exp.gs, key + " scale_grad")
+        if qc.learn_zp:
+            _same_class(gz, exp.gz, key + " zp_grad")
+        rec = dict(kind="learnable_fq_edges", key=key, qcase=qc.name, variant=variant, sym=qc.sym, bits=qc.bits,
+                   learn_zp=qc.learn_zp, scale=repr(float(qc.scale)), zp=float(qc.zp), scale_grad=repr(gs),
+                   x=put(key + "_x", x), g=put(key + "_g", g), y=put(key + "_y", y), grad_x=put(key + "_gx", gx))
+        if qc.learn_zp:
+            rec.update(zp_grad=repr(gz))
+        cases.append(rec)
+
+# 10b. per_channel_learnable (4d) with three special channels among ordinary ones
+#      (EC.pc_build): a NaN gradient on an in-range element, a negative scale, a channel
+#      clamped everywhere.
+pce_idx = 0
+for sym, bits in ((True, 8), (True, 4), (False, 8), (False, 4)):
+    w, gg, s0, z0 = EC.pc_build((6, 5, 3, 3), 0, sym, bits, seed=90 + pce_idx, learn_zp=not sym)
+    q = UniformQuantizer(bits, sym)
+    ys, gxs, gss, gzs = [], [], [], []
+    for c in range(w.shape[0]):
+        sc = torch.nn.Parameter(torch.tensor(np.float64(s0[c])))
+        zc = 0 if sym else torch.nn.Parameter(torch.tensor(np.float64(z0[c])))
+        xr = torch.from_numpy(w[c].copy()).requires_grad_(True)
+        y = q.quantize(xr, sc, zc, True)
+        y.backward(torch.from_numpy(gg[c].copy()))
+        ys.append(y.detach())
+        gxs.append(xr.grad.detach())
+        gss.append(float(sc.grad))
+        gzs.append(0.0 if sym else float(zc.grad))
+    key = f"pcle{pce_idx}"
+    pce_idx += 1
+    exp = EC.pc_oracle(w, gg, s0, z0, q.qmin, q.qmax, NPO.grad_scale(q.qmax, w[0].size), 0, not sym)
+    for c in range(w.shape[0]):
+        _same_class(gss[c], exp.gs[c], f"{key} scale_grad[{c}]")
+        if not sym:
+            _same_class(gzs[c], exp.gz[c], f"{key} zp_grad[{c}]")
+    assert np.isnan(gss[1]) and (sym or np.isnan(gzs[1])), key   # the NaN-gradient channel says so
+    cases.append(dict(kind="per_channel_learnable_edges", key=key, sym=sym, bits=bits, x=put(key + "_x", w),
+                      g=put(key + "_g", gg), scale=put(key + "_scale", s0), zp=put(key + "_zp", z0),
+                      y=put(key + "_y", torch.stack(ys)), grad_x=put(key + "_gx", torch.stack(gxs)),
+                      scale_grad=put(key + "_gs", torch.tensor(gss, dtype=torch.float64)),
+                      zp_grad=put(key + "_gz", torch.tensor(gzs, dtype=torch.float64))))
+
+# 10c. LSQFakeQuantize (7) per channel along axis 1 with given parameters: channel 1
+#      carries a NaN gradient on an in-range element, channel 4 a +inf and a -inf x.
+torch.manual_seed(777)
+fq = LSQFakeQuantize(learn_scale=True, config_act=False,
+                     observer=torch.quantization.MovingAveragePerChannelMinMaxObserver,
+                     quant_min=0, quant_max=255, dtype=torch.quint8,
+                     qscheme=torch.per_channel_affine, reduce_range=False,
+                     averaging_constant=0.01, ch_axis=1)
+shape = (4, 6, 9, 9)
+for _ in range(3):
+    fq(torch.randn(shape) * 1.5 + 0.3)
+fq.disable_observer()
+x = torch.randn(shape) * 1.5 + 0.3
+gg = torch.randn(shape)
+s1, z1 = float(fq.scale_param.detach().reshape(-1)[1]), float(fq.zero_point_param_float.detach().reshape(-1)[1])
+assert 0 <= round(z1) <= 255
+x[0, 1, 0, 0] = 0.25 * s1                                  # x / s + round(zp) in range
+gg[0, 1, 0, 0] = float("nan")
+x[1, 4, 2, 3] = float("inf")
+x[2, 4, 5, 1] = float("-inf")
+xr = x.clone().requires_grad_(True)
+y = fq(xr)
+y.backward(gg)
+key = f"lsqm{lsqm_idx}"
+lsqm_idx += 1
+exp = EC.pc_oracle(x.numpy(), gg.numpy(), fq.scale_param.detach().reshape(-1).numpy(),
+                   fq.zero_point_param_float.detach().reshape(-1).numpy(), 0, 255,
+                   NPO.lsq_module_grad_scale(shape, 255, True, False), 1, True)
+for c in range(shape[1]):
+    _same_class(float(fq.scale_param.grad.reshape(-1)[c]), exp.gs[c], f"{key} scale_grad[{c}]")
+    _same_class(float(fq.zero_point_param_float.grad.reshape(-1)[c]), exp.gz[c], f"{key} zp_grad[{c}]")
+assert torch.isnan(fq.zero_point_param_float.grad.reshape(-1)[1]), key
+cases.append(dict(kind="lsq_fake_quantize", key=key, per_channel=True, config_act=False, edges=True,
+                  qmin=0, qmax=255, x=put(key + "_x", x), g=put(key + "_g", gg), y=put(key + "_y", y),
+                  grad_x=put(key + "_gx", xr.grad),
+                  scale=put(key + "_scale", fq.scale_param.detach()),
+                  zp=put(key + "_zp", fq.zero_point_param_float.detach()),
+                  scale_grad=put(key + "_sgrad", fq.scale_param.grad),
+                  zp_grad=put(key + "_zgrad", fq.zero_point_param_float.grad)))
+
 # several archives, each well below 1 MiB: a new one once 700 KiB of raw data are in the last
 shards, size = [{}], 0
 for k, v in arrays.items():
@@ -697,8 +820,21 @@ for k, v in arrays.items():
         size = 0
     shards[-1][k] = v
     size += v.nbytes
+def _unchanged(path, shard):
+    """The archive at path holds exactly these arrays, bit for bit (then it is left alone:
+    rewriting it would change the file's bytes, not its content)."""
+    if not os.path.exists(path):
+        return False
+    with np.load(path, allow_pickle=False) as old:
+        return (set(old.files) == set(shard) and
+                all(old[k].dtype == v.dtype and old[k].shape == v.shape and old[k].tobytes() == v.tobytes()
+                    for k, v in shard.items()))
+
+
 for i, s in enumerate(shards):
-    np.savez_compressed(os.path.join(OUT, f"fakequant_goldens_{i}.npz"), **s)
+    path = os.path.join(OUT, f"fakequant_goldens_{i}.npz")
+    if not _unchanged(path, s):
+        np.savez_compressed(path, **s)
 with open(os.path.join(OUT, "cases.json"), "w") as f:
     json.dump({"generator": "tests/golden/gen_goldens.py", "torch": torch.__version__,
                "reference": "tranngocduvnvp/VSIQuantization @ /root/reference", "cases": cases},

@@ -115,7 +115,10 @@ __device__ __forceinline__ float lsq_elem(float x, float g, const QP &p, LsqAcc 
     acc.t += (double)t1 + (double)t2;
     // AddBackward0 + SubBackward0 (other): gm + (-gq) is +0 when in range (acc starts at
     // +0 and never becomes -0, so adding +0 is a no-op) and -gq when clamped -- the same
-    // bits with one conversion and one f64 add fewer
+    // bits with one conversion and one f64 add fewer.  That needs gq finite: for gq NaN
+    // or +-inf the reference's sum is NaN (it holds NaN, or inf + -inf).  No such gq
+    // arrives here: lsq_fast_ok4x bounds every in-range |g| by 2^63 and ste_fast_s bounds
+    // s by 2^60, so an in-range |g * s| <= 2^123; the two slower paths below form the sum.
     if (ZPL) acc.z += e.m ? 0.0 : -(double)gq;
     // DivBackward0 (self): ste_quot_d from the product already formed; 0/s signed like IEEE
     const float qd = __builtin_copysignf(__builtin_fmaf(__builtin_fmaf(-g, p.d.b, gq), p.d.r, g), gq);
@@ -133,7 +136,11 @@ __device__ __forceinline__ float lsq_elem(float x, float g, const QP &p, LsqAcc 
   // lanes past the tensor's end (valid false) add +0 terms: selects, not exec branches
   // (acc starts at +0.0, so adding +0.0 never changes its bits)
   acc.t += valid ? (double)t1 + (double)t2 : 0.0;
-  if (ZPL) acc.z += (valid && !m) ? -(double)gq : 0.0;   // AddBackward0 + SubBackward0 (other), as above
+  // AddBackward0 + SubBackward0 (other): gm + (-gq).  In range that is gq - gq: +0 for a
+  // finite gq, NaN for gq NaN or +-inf (an incoming NaN / inf gradient, or g * s
+  // overflowing) -- the reference's zero-point gradient is NaN then, so the term is formed
+  // and not taken as +0; these paths are the ones such a gq reaches (fdiv_ok(gm) fails)
+  if (ZPL) acc.z += valid ? (double)(m ? gq - gq : -gq) : 0.0;
   return fdiv_t<IEEE>(gm, p.d);             // DivBackward0 (self)
 }
 

@@ -305,6 +305,8 @@ class LsqSpec:
     __slots__ = ("scale", "zero_point", "qmin", "qmax", "gscale", "learn_zp")
 
     def __init__(self, scale, zero_point, qmin, qmax, gscale, learn_zp):
+        if int(learn_zp) not in (0, 1):   # mode 2 (zp as given, no ScaleGradient) is the per-tensor K4's alone
+            raise ValueError(f"multi-tensor learnable fake quant: learn_zp must be 0 or 1, got {learn_zp!r}")
         self.scale, self.zero_point = scale, zero_point
         self.qmin, self.qmax, self.gscale, self.learn_zp = int(qmin), int(qmax), float(gscale), bool(learn_zp)
 

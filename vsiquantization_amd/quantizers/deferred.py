@@ -56,7 +56,11 @@ class _Fold:
 def lsq_backward_part(g, x, scale, zero_point, qmin, qmax, learn_zp, act, records):
     """K4 records-only: grad_x; the call's per-workgroup {sum t, sum z} into ``records``.
     bfloat16 / float16 g and x (the same dtype): grad_x is the fp32 call's on the widened
-    tensors rounded once to that dtype, the records are the fp32 call's bit for bit."""
+    tensors rounded once to that dtype, the records are the fp32 call's bit for bit.
+    learn_zp 2 (a zero point used as given, no ScaleGradient) is K4's alone: the fold
+    knows the rounded, clamped zero point only, so it raises here."""
+    if int(learn_zp) not in (0, 1):
+        raise ValueError(f"records-only learnable backward: learn_zp must be 0 or 1, got {learn_zp!r}")
     g, dt = H.require_device_float(g, "grad_output")
     x = H.require_same_dtype(x, g, "x")
     dev = g.device
