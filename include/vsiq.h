@@ -597,6 +597,38 @@ int vsiq_act_observe_mse_f32(const float *c, int64_t n, int act, const double *s
                              float *run_minmax, double *qp_out, double *clip_out, double *err_out,
                              int32_t *pick_out, int symmetric, double qden, double eps, void *stream);
 int64_t vsiq_observe_mse_ws_doubles(int64_t n, int count);
+/*
+ * The per-channel MSE observer (PerChannelMSEObserver; added within ABI 13: purely additive):
+ * observe, search, running update, f64 qparams and optionally the fake quant of every row of
+ * a row-major [rows, rowlen] fp32 view in ONE launch and one read of the tensor.  Row c is
+ * processed exactly as vsiq_act_observe_mse_f32 (act = none) defines it for the tensor W[c]:
+ *   mn, mx and the NaN flag are the row's own (NaN-ignoring fp32 min / max and "the row holds
+ *   a NaN", as vsiq_pc_observe_fq_f32 reduces a row);
+ *   lo_k = (float)((double)mn * r[k]), hi_k = (float)((double)mx * r[k]); validity, E_k, the
+ *   strict-< pick from k = 0 and the end of the call -- the running update of (run_min[c],
+ *   run_max[c]) with (lo_k*, hi_k*) and the f64 qparams of the updated state -- follow the
+ *   per-tensor definition above.
+ * Fallback is per row: row c is vsiq_pc_observe_fq_f32's ((lo, hi) = (mn, mx), pick 0, its
+ * errors all +inf) when the row holds a NaN, mn == mx, mn or mx is not finite, or count == 1;
+ * one row's fallback never affects another row.
+ * The terms are fixed by the definition; the order of each row's f64 sum is the
+ * implementation's, fixed per (rowlen, count): no floating-point atomics, the same bits run
+ * to run.
+ * Outputs: run_min / run_max fp32[rows] in/out, scale_out / zp_out f64[rows] (from the running
+ * state after the update, as K3), clip_out f64[rows][2] = (lo, hi), err_out f64[rows][count]
+ * (nullable), pick_out int32[rows], row_stats f64[rows][3] (nullable; sum|x|, sum x, sum x^2).
+ * With y != NULL, row c of y (and mask / codes) is vsiq_pc_fq_fwd_f32's output for the qparams
+ * this call returns for row c, bit for bit; y == NULL observes only (codes and mask must then
+ * be NULL too).  `ratios` is a HOST f64[count] and travels by value with the launch (the call
+ * captures into a HIP graph); no workspace and no counter: a row never spans workgroups.
+ * VSIQ_E_ARG: a null among x, run_min, run_max, scale_out, zp_out, clip_out, pick_out, ratios;
+ * rows <= 0 or rowlen <= 0; codes or mask without y; count outside [1, 128], ratios[0] != 1,
+ * a ratio outside (0, 1] or NaN; qmin >= qmax.  fp32 only, axis 0 only.
+ */
+int vsiq_pc_observe_mse_f32(const float *x, float *y, void *codes, uint64_t *mask, int64_t rows, int64_t rowlen,
+                            const double *ratios, int count, float *run_min, float *run_max, double *scale_out,
+                            double *zp_out, double *clip_out, double *err_out, int32_t *pick_out, double *row_stats,
+                            int symmetric, int qmin, int qmax, double qden, double eps, void *stream);
 int vsiq_act_ste_bwd_f32(const float *g, const uint64_t *mask, const float *c, float *gc, int64_t n,
                          int act, const double *scale_dev, int64_t rowlen, double scale_host,
                          void *stream);
@@ -764,6 +796,13 @@ int vsiq_host_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t n, 
 int vsiq_host_pc_observe_fq_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen,
                                 float *run_min, float *run_max, double *scale_out, double *zp_out,
                                 double *row_stats, int symmetric, double qden, double eps, int qmin, int qmax);
+/* vsiq_pc_observe_mse_f32 on the host: vsiq_host_observe_f32 and vsiq_host_observe_mse_f32 on
+ * each row alone, then vsiq_host_pc_fq_fwd_f32 with the qparams returned (mask: one byte per
+ * element; no codes).  The same argument errors. */
+int vsiq_host_pc_observe_mse_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen,
+                                 const double *ratios, int count, float *run_min, float *run_max, double *scale_out,
+                                 double *zp_out, double *clip_out, double *err_out, int32_t *pick_out,
+                                 double *row_stats, int symmetric, int qmin, int qmax, double qden, double eps);
 int vsiq_host_pc_fq_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen,
                             const double *scale, const double *zp, int zp_round, int qmin, int qmax);
 int vsiq_host_pc_ste_bwd_f32(const float *g, const uint8_t *mask, float *gx, int64_t rows, int64_t rowlen,

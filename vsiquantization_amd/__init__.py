@@ -8,6 +8,7 @@ Importing the package registers the quantizer/observer classes by name in
   LSQQuantizer, LSQObserver                         (names the reference README advertises)
   PerChannelUniformQuantizer, PerChannelMinMaxObserver  (per-channel, axis 0)
   PercentileObserver, MSEObserver                   (calibrators that clip the min / max range)
+  PerChannelMSEObserver                             (MSEObserver's search on every out-channel row)
 
 plus ``LSQFakeQuantize`` (quantizers/lsq_module.py, the torch.ao-based LSQ module).
 All fake-quant arithmetic runs in the HIP kernels of ``csrc/`` through the C ABI of
@@ -27,6 +28,7 @@ from .observers.minmax import LSQObserver  # noqa: F401
 from .observers.per_channel import PerChannelMinMaxObserver  # noqa: F401
 from .observers.percentile import PercentileObserver  # noqa: F401
 from .observers.mse import MSEObserver  # noqa: F401
+from .observers.per_channel_mse import PerChannelMSEObserver  # noqa: F401
 from .quantizers.quantization_manager import QuantizationManager  # noqa: F401
 from .quantizers.fake_quantize import FakeQuantize  # noqa: F401
 from .quantizers.lsq_module import LSQFakeQuantize  # noqa: F401

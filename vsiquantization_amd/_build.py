@@ -49,7 +49,8 @@ FLAGS = [
 # built with.  k_observe_hist.hip (the percentile observer's histogram pass; picked up by
 # sources() like every csrc/*.hip) has no fp32 |x| sums to keep scalar: default flags, and
 # k_observe_mse.hip (the MSE observer's error-search pass) is built as it is: like every file
-# never contracted (-ffp-contract=off in FLAGS), which its per-term f64 arithmetic relies on.
+# never contracted (-ffp-contract=off in FLAGS), which its per-term f64 arithmetic relies on;
+# k_pc_mse.hip (the per-channel search, the same wave step from k_mse_step.cuh) likewise.
 _NO_SLP = ["-fno-slp-vectorize"]
 FILE_FLAGS = {"k_observe.hip": _NO_SLP, "k_observe_half.hip": _NO_SLP, "k_observe_fq.hip": _NO_SLP,
               "k_lib.hip": _NO_SLP}

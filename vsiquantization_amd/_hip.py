@@ -206,6 +206,8 @@ _SIGS = {
     "vsiq_act_observe_mse_f32": ([c_p, c_i64, c_int, c_p, c_p, c_int, c_int, c_int, c_p, c_i64, c_p, c_p, c_p, c_p, c_p,
                                   c_p, c_int, c_d, c_d, c_p], c_int),
     "vsiq_observe_mse_ws_doubles": ([c_i64, c_int], c_i64),
+    "vsiq_pc_observe_mse_f32": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                 c_int, c_int, c_int, c_d, c_d, c_p], c_int),
     "vsiq_observe_part_records": ([c_i64], c_i64),
     "vsiq_observe_part_out_records": ([c_i64], c_i64),
     "vsiq_act_observe_part_f32": ([c_p, c_i64, c_int, c_p, c_i64, c_p], c_int),
@@ -237,6 +239,8 @@ _SIGS = {
     "vsiq_host_lsq_bwd_f32": ([c_p, c_p, c_p, c_i64, c_int, c_d, c_d, c_int, c_int, c_int, c_d, c_p], c_int),
     "vsiq_host_pc_observe_fq_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_int, c_d, c_d, c_int,
                                      c_int], c_int),
+    "vsiq_host_pc_observe_mse_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                      c_int, c_int, c_int, c_d, c_d], c_int),
     "vsiq_host_pc_fq_fwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int], c_int),
     "vsiq_host_pc_ste_bwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p], c_int),
     "vsiq_host_pcm_fq_fwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int], c_int),

@@ -608,6 +608,45 @@ int vsiq_host_pc_observe_fq_f32(const float *x, float *y, uint8_t *mask, int64_t
   return rc.load();
 }
 
+// PerChannelMSEObserver on CPU tensors (vsiq_pc_observe_mse_f32's definition): each row the
+// per-tensor host calls above on that row alone -- vsiq_host_observe_f32 for the row's record
+// and sums, vsiq_host_observe_mse_f32 on the row's own running state -- then the per-channel
+// host fake quant with the qparams just returned.
+int vsiq_host_pc_observe_mse_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen,
+                                 const double *ratios, int count, float *run_min, float *run_max, double *scale_out,
+                                 double *zp_out, double *clip_out, double *err_out, int32_t *pick_out,
+                                 double *row_stats, int symmetric, int qmin, int qmax, double qden, double eps) {
+  if (rows <= 0 || rowlen <= 0 || !x || !run_min || !run_max || !scale_out || !zp_out || !clip_out || !pick_out)
+    return VSIQ_E_ARG;
+  if (!y && mask) return VSIQ_E_ARG;
+  if (!mse_ratios_ok(ratios, count) || qmin >= qmax) return VSIQ_E_ARG;
+  std::atomic<int> rc{0};
+  Pool::get().run(rows, [&](int64_t r) {
+    const float *xr = x + r * rowlen;
+    float st[2] = {run_min[r], run_max[r]};
+    double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN], err[kMseMaxCand];
+    int e = vsiq_host_observe_f32(xr, rowlen, kActNone, stats, nullptr, nullptr, symmetric, qden, eps);
+    if (!e)
+      e = vsiq_host_observe_mse_f32(xr, rowlen, kActNone, stats, ratios, count, qmin, qmax, st, qp, clip_out + 2 * r,
+                                    err_out ? err_out + r * count : err, pick_out + r, symmetric, qden, eps);
+    if (e) {
+      rc.store(e);
+      return;
+    }
+    run_min[r] = st[0];
+    run_max[r] = st[1];
+    scale_out[r] = qp[VSIQ_QP_SCALE];
+    zp_out[r] = qp[VSIQ_QP_ZP];
+    if (row_stats) {
+      row_stats[3 * r] = stats[VSIQ_ST_SUMABS];
+      row_stats[3 * r + 1] = stats[VSIQ_ST_SUM];
+      row_stats[3 * r + 2] = stats[VSIQ_ST_SUMSQ];
+    }
+  });
+  if (rc.load() || !y) return rc.load();
+  return vsiq_host_pcm_fq_fwd_f32(x, y, mask, rows, rowlen, rows, scale_out, zp_out, 0, qmin, qmax);
+}
+
 int vsiq_host_pc_fq_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen,
                             const double *scale, const double *zp, int zp_round, int qmin, int qmax) {
   return vsiq_host_pcm_fq_fwd_f32(x, y, mask, rows, rowlen, rows > 0 ? rows : 1, scale, zp, zp_round, qmin, qmax);

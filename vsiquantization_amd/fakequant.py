@@ -980,3 +980,74 @@ class PerChannelObserveFQFn(torch.autograd.Function):
         mask, scale = ctx.saved_tensors
         gx = ste_backward(gy.contiguous(), mask, scale, ctx.rowlen)
         return gx, None, None, None, None, None, None, None, None
+
+
+# --------------------------------------------------------------------------- per-channel MSE
+def per_channel_observe_mse(x: torch.Tensor, *, symmetric: bool, qmin: int, qmax: int, num_bits: int = 8,
+                            eps: float = 1e-8, run_min=None, run_max=None, ratios, quantize: bool = True,
+                            want_row_stats: bool = False, want_mask: bool = False):
+    """Per-channel (axis 0) MSE observe + f64 qparams + fake quant in one launch and one read
+    of the tensor (csrc/k_pc_mse.hip): every row W[c] searched as observe_mse searches a tensor
+    -- its own min / max, its own candidates ratios[k] * (min, max) scored on the grid (qmin,
+    qmax), its own pick and fallback -- then the running update of (run_min[c], run_max[c]) and
+    the row's f64 qparams (include/vsiq.h states the definition).
+
+    quantize=False observes only (y is None).  Returns per_channel_observe_fq's dict plus
+    clip f64[C, 2] = (lo, hi), err f64[C, len(ratios)], pick int32[C].  fp32 only; CPU tensors:
+    the native host loop (host.pc_observe_mse)."""
+    r = check_mse_ratios(ratios)
+    qmin, qmax = int(qmin), int(qmax)
+    if qmin >= qmax:
+        raise ValueError(f"qmin must be below qmax, got ({qmin}, {qmax})")
+    if _host.is_host(x):
+        return _host.pc_observe_mse(x, symmetric=symmetric, qmin=qmin, qmax=qmax, num_bits=num_bits, eps=eps,
+                                    run_min=run_min, run_max=run_max, ratios=r, quantize=quantize,
+                                    want_row_stats=want_row_stats, want_mask=want_mask)
+    x = H.require_device_f32(x)
+    dev = x.device
+    C = x.shape[0] if x.dim() > 0 else 1
+    rowlen = x.numel() // max(C, 1)
+    if run_min is None or run_max is None:   # fresh observer state 0/0 (minmax.py:28-29), one fill
+        state = torch.zeros(2, C, dtype=torch.float32, device=dev)
+        run_min = state[0] if run_min is None else run_min
+        run_max = state[1] if run_max is None else run_max
+    if run_min.numel() != C or run_max.numel() != C:
+        raise ValueError(f"running state has {run_min.numel()} channels, tensor has {C}")
+    y = torch.empty_like(x) if quantize else None
+    scale = torch.empty(C, dtype=torch.float64, device=dev)
+    zp = torch.empty(C, dtype=torch.float64, device=dev)
+    clip = torch.empty(C, 2, dtype=torch.float64, device=dev)
+    err = torch.empty(C, len(r), dtype=torch.float64, device=dev)
+    pick = torch.empty(C, dtype=torch.int32, device=dev)
+    mask = H.mask_buffer(C, rowlen, dev) if (want_mask and quantize) else None
+    rstats = torch.empty(C, 3, dtype=torch.float64, device=dev) if want_row_stats else None
+    table = (H.c_d * len(r))(*r)
+    rc = H.lib().vsiq_pc_observe_mse_f32(H.ptr(x), H.ptr(y), None, H.ptr(mask), _i64(C), _i64(rowlen), table, len(r),
+                                         H.ptr(run_min), H.ptr(run_max), H.ptr(scale), H.ptr(zp), H.ptr(clip),
+                                         H.ptr(err), H.ptr(pick), H.ptr(rstats), int(bool(symmetric)), qmin, qmax,
+                                         qden(symmetric, num_bits, eps), float(eps), H.stream_of(dev))
+    H.check(rc, "vsiq_pc_observe_mse_f32")
+    return dict(y=y, scale=scale, zp=zp, run_min=run_min, run_max=run_max, mask=mask, codes=None, row_stats=rstats,
+                clip=clip, err=err, pick=pick)
+
+
+class PerChannelObserveMSEFn(torch.autograd.Function):
+    """per_channel_observe_mse with the STE backward (row c uses fp32(scale_c)), in the style
+    of PerChannelObserveFQFn.  Returns (y, scale, zp, row_stats, err, pick)."""
+
+    @staticmethod
+    def forward(ctx, x, symmetric, qmin, qmax, num_bits, eps, run_min, run_max, ratios, want_row_stats):
+        r = per_channel_observe_mse(x, symmetric=symmetric, qmin=qmin, qmax=qmax, num_bits=num_bits, eps=eps,
+                                    run_min=run_min, run_max=run_max, ratios=ratios, want_mask=True,
+                                    want_row_stats=want_row_stats)
+        ctx.save_for_backward(r["mask"], r["scale"])
+        ctx.rowlen = x.numel() // x.shape[0]
+        rs = r["row_stats"] if want_row_stats else r["scale"].new_zeros(0)
+        ctx.mark_non_differentiable(r["scale"], r["zp"], rs, r["err"], r["pick"])
+        return r["y"], r["scale"], r["zp"], rs, r["err"], r["pick"]
+
+    @staticmethod
+    def backward(ctx, gy, _gs, _gz, _gr, _ge, _gp):
+        mask, scale = ctx.saved_tensors
+        gx = ste_backward(gy.contiguous(), mask, scale, ctx.rowlen)
+        return gx, None, None, None, None, None, None, None, None, None

@@ -251,6 +251,40 @@ def pc_observe_fq(x, *, symmetric, qmin, qmax, obs_bits=8, eps=1e-8, run_min=Non
                 row_stats=rstats)
 
 
+def pc_observe_mse(x, *, symmetric, qmin, qmax, num_bits=8, eps=1e-8, run_min=None, run_max=None, ratios,
+                   quantize=True, want_row_stats=False, want_mask=False):
+    """Host counterpart of fakequant.per_channel_observe_mse (which has validated ``ratios``
+    and the grid): the host MSE loop on each row W[c] with its own running state, then the
+    host per-channel fake quant with the qparams returned.  Same dict as the device function."""
+    from .fakequant import qden
+    x = _f32(x)
+    C, rowlen = _rows(x)
+    if run_min is None or run_max is None:
+        state = torch.zeros(2, C, dtype=torch.float32)
+        run_min = state[0] if run_min is None else run_min
+        run_max = state[1] if run_max is None else run_max
+    for r in (run_min, run_max):
+        if r.numel() != C or r.device.type != "cpu" or r.dtype != torch.float32 or not r.is_contiguous():
+            raise ValueError(f"host per-channel observe: running state must be contiguous CPU float32 [{C}]")
+    y = torch.empty_like(x) if quantize else None
+    mask = torch.empty(x.shape, dtype=torch.uint8) if (want_mask and quantize) else None
+    scale = torch.empty(C, dtype=torch.float64)
+    zp = torch.empty(C, dtype=torch.float64)
+    clip = torch.empty(C, 2, dtype=torch.float64)
+    err = torch.empty(C, len(ratios), dtype=torch.float64)
+    pick = torch.empty(C, dtype=torch.int32)
+    rstats = torch.empty(C, 3, dtype=torch.float64) if want_row_stats else None
+    table = (H.c_d * len(ratios))(*ratios)
+    rc = H.lib().vsiq_host_pc_observe_mse_f32(H.ptr(x), H.ptr(y), H.ptr(mask), _i64(C), _i64(rowlen), table,
+                                              len(ratios), H.ptr(run_min), H.ptr(run_max), H.ptr(scale), H.ptr(zp),
+                                              H.ptr(clip), H.ptr(err), H.ptr(pick), H.ptr(rstats),
+                                              int(bool(symmetric)), int(qmin), int(qmax),
+                                              qden(symmetric, num_bits, eps), float(eps))
+    H.check(rc, "vsiq_host_pc_observe_mse_f32")
+    return dict(y=y, scale=scale, zp=zp, run_min=run_min, run_max=run_max, mask=mask, codes=None, row_stats=rstats,
+                clip=clip, err=err, pick=pick)
+
+
 def pc_fake_quant(x, scale, zp, qmin, qmax, *, zp_round=False, want_mask=False, axis=0):
     """Per-channel fake quant with given [C] qparams along ``axis`` 0 or 1 on the host:
     (y, mask | None)."""
@@ -312,6 +346,25 @@ class PcObserveFQFn(torch.autograd.Function):
         return pc_ste_backward(gy, mask, scale), None, None, None, None, None, None, None, None
 
 
+class PcObserveMSEFn(torch.autograd.Function):
+    """pc_observe_mse with the STE backward, on the host: (y, scale, zp, row_stats, err, pick)."""
+
+    @staticmethod
+    def forward(ctx, x, symmetric, qmin, qmax, num_bits, eps, run_min, run_max, ratios, want_row_stats):
+        r = pc_observe_mse(x, symmetric=symmetric, qmin=qmin, qmax=qmax, num_bits=num_bits, eps=eps,
+                           run_min=run_min, run_max=run_max, ratios=ratios, want_mask=True,
+                           want_row_stats=want_row_stats)
+        ctx.save_for_backward(r["mask"], r["scale"])
+        rs = r["row_stats"] if want_row_stats else r["scale"].new_zeros(0)
+        ctx.mark_non_differentiable(r["scale"], r["zp"], rs, r["err"], r["pick"])
+        return r["y"], r["scale"], r["zp"], rs, r["err"], r["pick"]
+
+    @staticmethod
+    def backward(ctx, gy, _gs, _gz, _gr, _ge, _gp):
+        mask, scale = ctx.saved_tensors
+        return pc_ste_backward(gy, mask, scale), None, None, None, None, None, None, None, None, None
+
+
 class PcLearnFn(torch.autograd.Function):
     """Learnable per-channel fake quant on the host (``axis`` 0: [C, ...] weights, 1:
     [N, C, ...] activations -- LSQFakeQuantize): each row the per-tensor learnable host
@@ -362,5 +415,5 @@ def simd() -> bool:
 
 
 __all__ = ["is_host", "fake_quant", "fake_quant_fixed", "fake_quant_learn", "observe_tensor", "observe_percentile",
-           "observe_mse", "pc_observe_fq",
+           "observe_mse", "pc_observe_fq", "pc_observe_mse",
            "pc_fake_quant", "threads", "simd"]
