@@ -32,6 +32,13 @@
  *     vsiq_mask_words(rows, rowlen) gives the word count; 8-byte alignment.
  *   - Codes are int8 (symmetric) or uint8 (asymmetric) holding
  *     clamp(round(x/s+zp)); NaN inputs give code 0.
+ *   - Packed codes (the export format, vsiq_quantize_pack_f32): unsigned fields of
+ *     `bits` in {2, 4, 8} holding code - qmin.  A tensor is viewed as `rows` rows of
+ *     `rowlen` elements (per-tensor: one row of n); row r starts at byte r * row_bytes,
+ *     row_bytes = 4 * ceil(rowlen * bits / 32) = vsiq_packed_row_bytes(rowlen, bits);
+ *     element e of a row lives in byte e * bits / 8 of the row at bit offset
+ *     (e % (8 / bits)) * bits (little-endian within the byte).  Every padding bit is 0,
+ *     so two buffers of the same tensor compare byte for byte.  4-byte alignment.
  */
 #ifndef VSIQ_H_
 #define VSIQ_H_
@@ -742,6 +749,48 @@ int vsiq_pcm_lsq_bwd_arrive_f32(const float *g, const float *x, float *gx, int64
                                 int qmin, int qmax, double gscale, double *grad_scale_out,
                                 double *grad_zp_out, double *ws, int64_t ws_len, uint32_t *counters,
                                 int64_t counters_len, void *stream);
+
+/*
+ * Export (added within ABI 13: purely additive, no existing entry changes): trained
+ * weights as packed 2 / 4 / 8-bit codes plus the fp32 qparams that reproduce them, and
+ * the inverse.  Layout: "Packed codes" in the conventions above.
+ *
+ * vsiq_quantize_pack_f32: x is a row-major fp32 [rows, rowlen] view; scale / zp are f64
+ * device arrays of nq entries, nq == 1 (one pair for the tensor) or nq == rows (row r uses
+ * entry r); zp NULL means 0.  Per element the code is the forward kernels' own
+ *   q = clamp(rint(x / s + z), qmin, qmax),  s = fp32(scale), z = fp32(zp),
+ * with zp_round != 0 applying clamp(rint(zp), qmin, qmax) in f64 first and a NaN x giving
+ * code 0 (exactly vsiq_pc_fq_fwd_f32's `codes`); the field stored is q - qmin.
+ * qparams_out is fp32 [nq][2] and receives the (s, z) the kernel used, after zp_round:
+ * these two numbers ARE the export's qparams -- vsiq_unpack_dequant takes them as they
+ * are, so no host code ever re-derives a rounding.
+ * VSIQ_E_ARG: bits outside {2, 4, 8}, qmax - qmin + 1 > 2^bits, qmin > qmax, nq not 1 or
+ * rows, rowlen <= 0, a null among x / packed / qparams_out / scale, more than 2^32 - 256
+ * 16-element slots.  VSIQ_E_ALIGN: packed not 4-byte aligned.  rows == 0 returns 0.
+ *
+ * vsiq_unpack_dequant: y (nullable) has element type `dtype` (VSIQ_DT_*, below) and gets
+ *   y = (float(q) - z) * s      (fp32: the forward kernels' last two operations),
+ * rounded ONCE to nearest even for a 16-bit dtype; codes (nullable; int8 when qmin < 0,
+ * else uint8) gets q in the layout the forward kernels' `codes` output has.  qparams is
+ * the fp32 [nq][2] record of the pack call.  y is bit for bit the forward's y for the same
+ * (x, s, z) except where that y is -0.0 (or NaN): the forward keeps the sign of a value
+ * that rounds to -0.0 (and returns NaN for a NaN x); an integer code cannot, it gives +0.0
+ * (and code 0).  Same argument errors; an unknown dtype is VSIQ_E_ARG.
+ *
+ * No reduction, atomics, workspace or counter; both calls capture into a HIP graph.
+ * The host twins take HOST pointers, use the same layout and arithmetic (fp32 y only).
+ */
+int64_t vsiq_packed_row_bytes(int64_t rowlen, int bits);
+int vsiq_quantize_pack_f32(const float *x, void *packed, float *qparams_out, int64_t rows, int64_t rowlen,
+                           const double *scale, const double *zp, int64_t nq, int zp_round, int qmin, int qmax,
+                           int bits, void *stream);
+int vsiq_unpack_dequant(const void *packed, void *y, void *codes, int64_t rows, int64_t rowlen,
+                        const float *qparams, int64_t nq, int qmin, int bits, int dtype, void *stream);
+int vsiq_host_quantize_pack_f32(const float *x, void *packed, float *qparams_out, int64_t rows, int64_t rowlen,
+                                const double *scale, const double *zp, int64_t nq, int zp_round, int qmin, int qmax,
+                                int bits);
+int vsiq_host_unpack_dequant_f32(const void *packed, float *y, void *codes, int64_t rows, int64_t rowlen,
+                                 const float *qparams, int64_t nq, int qmin, int bits);
 
 /*
  * BatchNorm folding (modules/fused.py:100-108, :294-300), fp32, reference order:

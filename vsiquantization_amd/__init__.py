@@ -34,6 +34,8 @@ from .quantizers.fake_quantize import FakeQuantize  # noqa: F401
 from .quantizers.lsq_module import LSQFakeQuantize  # noqa: F401
 from .quantizers.foreach import enable_multi_tensor_weights, quantize_weights_multi  # noqa: F401
 from .quantizers.deferred import bundle_qparams, enable_deferred_qparam_grads  # noqa: F401
+from .fakequant import PackedTensor, quantize_pack, unpack_dequant  # noqa: F401
+from .utils.export import export_packed_state, packed_state_weights  # noqa: F401
 from .utils.quantize_manager import (disable_model_launches, enable_model_launches,  # noqa: F401
                                      model_launches_enabled)
 

@@ -51,6 +51,8 @@ FLAGS = [
 # k_observe_mse.hip (the MSE observer's error-search pass) is built as it is: like every file
 # never contracted (-ffp-contract=off in FLAGS), which its per-term f64 arithmetic relies on;
 # k_pc_mse.hip (the per-channel search, the same wave step from k_mse_step.cuh) likewise.
+# k_pack.hip (the export's quantize + pack and unpack + dequantize kernels) runs the forward
+# kernels' element code: default flags, like k_fq.hip and k_pc.hip.
 _NO_SLP = ["-fno-slp-vectorize"]
 FILE_FLAGS = {"k_observe.hip": _NO_SLP, "k_observe_half.hip": _NO_SLP, "k_observe_fq.hip": _NO_SLP,
               "k_lib.hip": _NO_SLP}

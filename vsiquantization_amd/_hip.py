@@ -266,6 +266,11 @@ _SIGS = {
                             c_p, c_p, c_i64, c_p, c_p], c_int),
     "vsiq_act_lsq_bwd_part_t": ([c_p, c_p, c_p, c_i64, c_int, c_int, c_p, c_d, c_p, c_d, c_int, c_int, c_int, c_p,
                                  c_i64, c_p], c_int),
+    "vsiq_packed_row_bytes": ([c_i64, c_int], c_i64),
+    "vsiq_quantize_pack_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_p], c_int),
+    "vsiq_unpack_dequant": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p], c_int),
+    "vsiq_host_quantize_pack_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_int], c_int),
+    "vsiq_host_unpack_dequant_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_int], c_int),
 }
 EXPORTED = tuple(_SIGS)
 

@@ -811,6 +811,68 @@ int vsiq_host_torch_mean_f32(const float *x, int64_t n, int act, int vec, int th
   return 0;
 }
 
+// The export format on the host (vsiq_quantize_pack_f32 / vsiq_unpack_dequant; layout in
+// vsiq.h): the element code of fq() above, fields packed with integer shifts, rows on the pool.
+int vsiq_host_quantize_pack_f32(const float *x, void *packed, float *qparams_out, int64_t rows, int64_t rowlen,
+                                const double *scale, const double *zp, int64_t nq, int zp_round, int qmin, int qmax,
+                                int bits) {
+  if (rows < 0 || rowlen <= 0 || (bits != 2 && bits != 4 && bits != 8) || qmin > qmax) return VSIQ_E_ARG;
+  if ((int64_t)qmax - (int64_t)qmin + 1 > (int64_t)1 << bits) return VSIQ_E_ARG;
+  if (rows == 0) return 0;
+  if ((nq != 1 && nq != rows) || !x || !packed || !qparams_out || !scale) return VSIQ_E_ARG;
+  const int64_t row_bytes = 4 * cdiv(rowlen * bits, 32);
+  const int per = 8 / bits;
+  const uint32_t fm = (1u << bits) - 1u;
+  uint8_t *out = (uint8_t *)packed;
+  for (int64_t c = 0; c < nq; ++c) {
+    const HQP p = make_hqp(scale[c], zp ? zp[c] : 0.0, zp_round, qmin, qmax);
+    qparams_out[2 * c] = p.s;
+    qparams_out[2 * c + 1] = p.z;
+  }
+  short_rows(rows, rowlen, [&](int64_t r) {
+    const int64_t c = nq == 1 ? 0 : r;
+    const HQP p{qparams_out[2 * c], qparams_out[2 * c + 1], (float)qmin, (float)qmax};
+    const float *xr = x + r * rowlen;
+    uint8_t *o = out + r * row_bytes;
+    for (int64_t b = 0; b < row_bytes; ++b) {
+      uint32_t byte = 0;
+      for (int k = 0; k < per; ++k) {
+        const int64_t e = b * per + k;
+        if (e >= rowlen) break;
+        bool m;
+        uint8_t code;
+        fq(xr[e], p, 0, &m, &code);
+        byte |= (((uint32_t)code - (uint32_t)qmin) & fm) << (k * bits);
+      }
+      o[b] = (uint8_t)byte;
+    }
+  });
+  return 0;
+}
+
+int vsiq_host_unpack_dequant_f32(const void *packed, float *y, void *codes, int64_t rows, int64_t rowlen,
+                                 const float *qparams, int64_t nq, int qmin, int bits) {
+  if (rows < 0 || rowlen <= 0 || (bits != 2 && bits != 4 && bits != 8)) return VSIQ_E_ARG;
+  if (rows == 0) return 0;
+  if ((nq != 1 && nq != rows) || !packed || !qparams) return VSIQ_E_ARG;
+  const int64_t row_bytes = 4 * cdiv(rowlen * bits, 32);
+  const int per = 8 / bits;
+  const uint32_t fm = (1u << bits) - 1u;
+  const uint8_t *in = (const uint8_t *)packed;
+  uint8_t *cd = (uint8_t *)codes;
+  short_rows(rows, rowlen, [&](int64_t r) {
+    const int64_t c = nq == 1 ? 0 : r;
+    const float s = qparams[2 * c], z = qparams[2 * c + 1];
+    const uint8_t *i = in + r * row_bytes;
+    for (int64_t e = 0; e < rowlen; ++e) {
+      const int q = (int)((i[e / per] >> ((e % per) * bits)) & fm) + qmin;
+      if (y) y[r * rowlen + e] = ((float)q - z) * s;
+      if (cd) cd[r * rowlen + e] = (uint8_t)(q & 0xff);
+    }
+  });
+  return 0;
+}
+
 int vsiq_host_threads(void) { return usable_cpus(); }
 
 int vsiq_host_simd(void) { return use_simd(kActNone) ? 1 : 0; }

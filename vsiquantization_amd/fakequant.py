@@ -1051,3 +1051,169 @@ class PerChannelObserveMSEFn(torch.autograd.Function):
         mask, scale = ctx.saved_tensors
         gx = ste_backward(gy.contiguous(), mask, scale, ctx.rowlen)
         return gx, None, None, None, None, None, None, None, None, None
+
+
+# --------------------------------------------------------------------------- export
+PACK_BITS = (2, 4, 8)
+
+
+class PackedTensor:
+    """A tensor exported as packed integer codes (layout: include/vsiq.h, "Packed codes").
+
+    data     uint8 [rows, row_bytes]: unsigned ``bits``-wide fields holding code - qmin
+    shape    the tensor's shape
+    bits     2, 4 or 8
+    qmin, qmax   the integer grid the codes lie on
+    qparams  fp32 [nq, 2]: the (scale, zero point) pairs the kernel used; nq = 1 (per tensor)
+             or shape[0] (per channel)
+    axis     0 (per channel along axis 0) or None (per tensor)
+
+    ``state()`` / ``from_state()`` map it to and from a dict of tensors, ints, a list and
+    None: plain data that torch.save / torch.load(weights_only=True) round-trips."""
+
+    __slots__ = ("data", "shape", "bits", "qmin", "qmax", "qparams", "axis")
+
+    def __init__(self, data, shape, bits, qmin, qmax, qparams, axis=None):
+        bits, qmin, qmax = int(bits), int(qmin), int(qmax)
+        shape = tuple(int(d) for d in shape)
+        if bits not in PACK_BITS:
+            raise ValueError(f"packed bits must be one of {PACK_BITS}, got {bits}")
+        if axis not in (None, 0):
+            raise ValueError(f"packed axis must be 0 or None, got {axis!r}")
+        if qmin > qmax or qmax - qmin + 1 > 2 ** bits:
+            raise ValueError(f"the grid [{qmin}, {qmax}] does not fit {bits}-bit fields")
+        rows, rowlen = _pack_view(shape, axis)
+        nq = rows if axis == 0 else 1
+        row_bytes = 4 * ((rowlen * bits + 31) // 32)
+        if data.dtype != torch.uint8 or tuple(data.shape) != (rows, row_bytes):
+            raise ValueError(f"packed data must be uint8 [{rows}, {row_bytes}] for shape {shape} at {bits} bits, "
+                             f"got {data.dtype} {tuple(data.shape)}")
+        if qparams.dtype != torch.float32 or tuple(qparams.shape) != (nq, 2):
+            raise ValueError(f"packed qparams must be float32 [{nq}, 2], got {qparams.dtype} {tuple(qparams.shape)}")
+        if qparams.device != data.device:
+            raise ValueError(f"packed data is on {data.device}, its qparams on {qparams.device}")
+        self.data, self.shape, self.bits, self.qmin, self.qmax = data, shape, bits, qmin, qmax
+        self.qparams, self.axis = qparams, axis
+
+    def state(self) -> dict:
+        return {"data": self.data, "shape": list(self.shape), "bits": self.bits, "qmin": self.qmin,
+                "qmax": self.qmax, "qparams": self.qparams, "axis": self.axis}
+
+    @classmethod
+    def from_state(cls, state: dict) -> "PackedTensor":
+        return cls(state["data"], state["shape"], state["bits"], state["qmin"], state["qmax"], state["qparams"],
+                   state["axis"])
+
+    def to(self, device) -> "PackedTensor":
+        return PackedTensor(self.data.to(device), self.shape, self.bits, self.qmin, self.qmax,
+                            self.qparams.to(device), self.axis)
+
+    def __repr__(self):
+        return (f"PackedTensor(shape={self.shape}, bits={self.bits}, grid=[{self.qmin}, {self.qmax}], "
+                f"axis={self.axis}, device={self.data.device})")
+
+
+def _pack_view(shape, axis):
+    """(rows, rowlen) of the row view: per tensor one row of numel, axis 0 one row per channel."""
+    n = 1
+    for d in shape:
+        n *= d
+    if n == 0:
+        raise ValueError(f"cannot pack an empty tensor (shape {tuple(shape)})")
+    if axis is None:
+        return 1, n
+    if len(shape) < 1:
+        raise ValueError("per-channel packing (axis=0) needs a tensor with at least one dim")
+    return shape[0], n // shape[0]
+
+
+def pack_bits_for(qmin: int, qmax: int) -> int:
+    """The smallest field width of 2 / 4 / 8 bits that holds the grid [qmin, qmax]."""
+    for b in PACK_BITS:
+        if qmax - qmin + 1 <= 2 ** b:
+            return b
+    raise ValueError(f"the grid [{qmin}, {qmax}] is wider than 8 bits")
+
+
+def _pack_scalar_f64(v, dev):
+    """A per-tensor qparam as an f64 [1] tensor on dev (a CUDA tensor is passed on without a sync)."""
+    if isinstance(v, torch.Tensor):
+        return _as_f64_device(v, dev).reshape(1)
+    if isinstance(v, (numbers.Real, np.floating, np.integer)):
+        return torch.tensor([float(v)], dtype=torch.float64, device=dev)
+    raise TypeError(f"unsupported qparam type {type(v).__name__}")
+
+
+def quantize_pack(x: torch.Tensor, scale, zero_point, qmin: int, qmax: int, *, bits=None, axis=None,
+                  zp_round: bool = False) -> PackedTensor:
+    """Quantize x to the integer codes clamp(rint(x/s + zp), qmin, qmax) of the forward
+    kernels (NaN -> code 0) and pack them into ``bits``-wide fields (None: the smallest of
+    2 / 4 / 8 that holds the grid): one launch, one read of x.  axis=None: scalar qparams;
+    axis=0: [C] qparams, one per out-channel row (zero_point None = 0).  The returned
+    PackedTensor carries the fp32 (scale, zero point) the kernel used, after ``zp_round``
+    (clamp(rint(zp), qmin, qmax), the learnable zero point's rounding); unpack_dequant
+    reproduces the forward's y from them.  A CPU tensor takes the native host loops."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"x must be a torch.Tensor, got {type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"x: only float32 is supported by the HIP fake-quant path, got {x.dtype}")
+    if not x.is_contiguous():
+        raise TypeError("x: quantize_pack needs a contiguous tensor (call .contiguous() first)")
+    qmin, qmax = int(qmin), int(qmax)
+    if bits is None:
+        bits = pack_bits_for(qmin, qmax)
+    bits = int(bits)
+    if bits not in PACK_BITS:
+        raise ValueError(f"packed bits must be one of {PACK_BITS}, got {bits}")
+    if qmin > qmax or qmax - qmin + 1 > 2 ** bits:
+        raise ValueError(f"the grid [{qmin}, {qmax}] does not fit {bits}-bit fields")
+    if axis not in (None, 0):
+        raise ValueError(f"quantize_pack: axis must be 0 or None, got {axis!r}")
+    rows, rowlen = _pack_view(x.shape, axis)
+    dev = x.device
+    if axis == 0:
+        nq = rows
+        as_t = lambda v: v if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
+        s = _per_channel_f64(as_t(scale), rows, dev, "scale")
+        z = _per_channel_f64(as_t(zero_point), rows, dev, "zero point") if zero_point is not None else None
+    else:
+        nq = 1
+        s = _pack_scalar_f64(scale, dev)
+        z = _pack_scalar_f64(zero_point, dev) if zero_point is not None else None
+    if dev.type == "cpu":
+        data, qparams = _host.quantize_pack(x, s, z, nq, rows, rowlen, qmin, qmax, bits, zp_round)
+        return PackedTensor(data, x.shape, bits, qmin, qmax, qparams, axis)
+    x = H.require_device_f32(x)
+    row_bytes = int(H.lib().vsiq_packed_row_bytes(_i64(rowlen), bits))
+    data = torch.empty((rows, row_bytes), dtype=torch.uint8, device=dev)
+    qparams = torch.empty((nq, 2), dtype=torch.float32, device=dev)
+    rc = H.lib().vsiq_quantize_pack_f32(H.ptr(x), H.ptr(data), H.ptr(qparams), _i64(rows), _i64(rowlen), H.ptr(s),
+                                        H.ptr(z), _i64(nq), int(bool(zp_round)), qmin, qmax, bits, H.stream_of(dev))
+    H.check(rc, "vsiq_quantize_pack_f32")
+    return PackedTensor(data, x.shape, bits, qmin, qmax, qparams, axis)
+
+
+def unpack_dequant(p: PackedTensor, dtype=torch.float32, want_codes: bool = False):
+    """The inverse of quantize_pack: y = (code - zp) * s in fp32 -- the forward kernels' last
+    two operations on the qparams the pack call recorded -- rounded once to ``dtype``
+    (float32 / bfloat16 / float16).  Returns y, or (y, codes) with the int8 (qmin < 0) /
+    uint8 codes in the layout ``want_codes`` of the fake-quant functions produces."""
+    if not isinstance(p, PackedTensor):
+        raise TypeError(f"unpack_dequant takes a PackedTensor, got {type(p).__name__}")
+    if dtype not in H._DT_CODES:
+        raise TypeError(f"unpack_dequant: float32, bfloat16 or float16 expected, got {dtype}")
+    rows, rowlen = _pack_view(p.shape, p.axis)
+    data, qparams = p.data.contiguous(), p.qparams.contiguous()
+    dev = data.device
+    if dev.type == "cpu":
+        y, codes = _host.unpack_dequant(data, qparams, p.shape, rows, rowlen, p.qmin, p.bits, want_codes)
+        y = y if dtype == torch.float32 else y.to(dtype)
+        return (y, codes) if want_codes else y
+    if dev.type != "cuda":
+        raise H.VsiqError(f"packed data is on {dev}: unpack_dequant runs on MI355X (HIP) or on CPU tensors")
+    y = torch.empty(p.shape, dtype=dtype, device=dev)
+    codes = torch.empty(p.shape, dtype=torch.int8 if p.qmin < 0 else torch.uint8, device=dev) if want_codes else None
+    rc = H.lib().vsiq_unpack_dequant(H.ptr(data), H.ptr(y), H.ptr(codes), _i64(rows), _i64(rowlen), H.ptr(qparams),
+                                     _i64(qparams.shape[0]), p.qmin, p.bits, H._DT_CODES[dtype], H.stream_of(dev))
+    H.check(rc, "vsiq_unpack_dequant")
+    return (y, codes) if want_codes else y

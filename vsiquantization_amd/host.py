@@ -416,4 +416,28 @@ def simd() -> bool:
 
 __all__ = ["is_host", "fake_quant", "fake_quant_fixed", "fake_quant_learn", "observe_tensor", "observe_percentile",
            "observe_mse", "pc_observe_fq", "pc_observe_mse",
-           "pc_fake_quant", "threads", "simd"]
+           "pc_fake_quant", "quantize_pack", "unpack_dequant", "threads", "simd"]
+
+
+# --------------------------------------------------------------------------- export
+def quantize_pack(x, scale, zp, nq, rows, rowlen, qmin, qmax, bits, zp_round):
+    """Host counterpart of fakequant.quantize_pack (which has checked the arguments):
+    (data uint8 [rows, row_bytes], qparams fp32 [nq, 2]) from f64 [nq] CPU qparams."""
+    row_bytes = int(H.lib().vsiq_packed_row_bytes(_i64(rowlen), int(bits)))
+    data = torch.empty((rows, row_bytes), dtype=torch.uint8)
+    qparams = torch.empty((nq, 2), dtype=torch.float32)
+    rc = H.lib().vsiq_host_quantize_pack_f32(H.ptr(x), H.ptr(data), H.ptr(qparams), _i64(rows), _i64(rowlen),
+                                             H.ptr(scale), H.ptr(zp), _i64(nq), int(bool(zp_round)), int(qmin),
+                                             int(qmax), int(bits))
+    H.check(rc, "vsiq_host_quantize_pack_f32")
+    return data, qparams
+
+
+def unpack_dequant(data, qparams, shape, rows, rowlen, qmin, bits, want_codes):
+    """Host counterpart of fakequant.unpack_dequant: (y fp32, codes | None)."""
+    y = torch.empty(shape, dtype=torch.float32)
+    codes = torch.empty(shape, dtype=torch.int8 if qmin < 0 else torch.uint8) if want_codes else None
+    rc = H.lib().vsiq_host_unpack_dequant_f32(H.ptr(data), H.ptr(y), H.ptr(codes), _i64(rows), _i64(rowlen),
+                                              H.ptr(qparams), _i64(qparams.shape[0]), int(qmin), int(bits))
+    H.check(rc, "vsiq_host_unpack_dequant_f32")
+    return y, codes

@@ -50,5 +50,14 @@ class FakeQuantize(nn.Module):
             return stash[1]
         return self.weight_quantizer.quantize(weights)
 
+    def export_packed_weight(self):
+        """(PackedTensor, bias) of this layer for deployment: the weight ``get_weight_bias()``
+        returns (the BN-folded one in the folded layers) as packed integer codes with the
+        weight quantizer's current qparams (QuantizationManager.export_packed), and the
+        bias as it is (detached; None if the layer has none)."""
+        w, b = self.get_weight_bias()
+        packed = self.weight_quantizer.export_packed(w.detach().contiguous())
+        return packed, (None if b is None else b.detach())
+
     def quantize_activation(self, out):
         return self.activation_quantizer.quantize(out)

@@ -479,6 +479,37 @@ class QuantizationManager(nn.Module):
                                            act=act)
         return x
 
+    def export_packed(self, x):
+        """``x`` as packed integer codes with this manager's CURRENT qparams (fakequant.
+        quantize_pack): what ``quantize(x)`` in eval computes, as integers plus the fp32
+        (scale, zero point) that reproduce it (fakequant.unpack_dequant).  Nothing changes:
+        no observer call, no stats record, scale / zero_point untouched; pending side-stream
+        observer work is joined first, as ``quantize`` does.  The zero point is rounded and
+        clamped exactly when the quantizer's learnable path would (``learn_args``); a [C]
+        scale under a PerChannelUniformQuantizer packs per channel (axis 0)."""
+        from ..fakequant import quantize_pack
+        from .lsq import LSQQuantizer
+        from .uniform import UniformQuantizer
+        q = self.quantizer
+        if type(q) not in (UniformQuantizer, LSQQuantizer, PerChannelUniformQuantizer):
+            raise NotImplementedError(f"export_packed supports UniformQuantizer, LSQQuantizer and "
+                                      f"PerChannelUniformQuantizer, not {type(q).__name__}")
+        self._join()
+        s, z = self.scale, self.zero_point
+        if isinstance(s, int) and not isinstance(s, bool) and s == 1:
+            raise RuntimeError("export_packed: this QuantizationManager has neither observed nor learned its "
+                               "qparams (scale is still 1 as constructed); calibrate or train it first")
+        per_channel = (isinstance(q, PerChannelUniformQuantizer)
+                       and any(isinstance(v, torch.Tensor) and v.dim() == 1 and v.numel() > 1 for v in (s, z)))
+        zp_round = False
+        if self.is_learning_scale:
+            if per_channel:   # PerChannelUniformQuantizer.quantize's learnable branch
+                zp_round = isinstance(z, torch.Tensor) and z.requires_grad
+            else:
+                _, z, learn_zp = q.learn_args(x, z)
+                zp_round = learn_zp == 1
+        return quantize_pack(x.detach(), s, z, q.qmin, q.qmax, axis=0 if per_channel else None, zp_round=zp_round)
+
     def _observe_deferred_act(self, x, act):
         """A fused layer's deferred calibration call (calibrate_qat_model's default mode):
         y = act(x), which the next layer consumes, and this call's K2p records of act(x) in
