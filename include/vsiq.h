@@ -793,6 +793,53 @@ int vsiq_host_unpack_dequant_f32(const void *packed, float *y, void *codes, int6
                                  const float *qparams, int64_t nq, int qmin, int bits);
 
 /*
+ * AdaRound: learned weight rounding (Nagel et al. 2020), two launches per optimisation
+ * step (added within ABI 13: purely additive).  w, V, y, g, grad_V are row-major fp32
+ * [rows, rowlen] views of the same shape; scale / zp / nq / zp_round / qmin / qmax as for
+ * vsiq_quantize_pack_f32 (s = fp32(scale), z = fp32(zp), lo = qmin, hi = qmax; a per-tensor
+ * call is rows = 1, nq = 1).  Per element, fp32 unless stated:
+ *   t   = RN(RN(w / s) + z)                  the forward kernels' quotient and add
+ *   b   = floor(t)
+ *   sig = 1 / (1 + sleef_expf_u10(-V))       IEEE division
+ *   hr  = fmaf(sig, 1.2, -0.1)               zeta = 1.1, gamma = -0.1
+ *   h   = min(max(hr, 0), 1)                 a NaN V gives h = 0
+ *   hp  = (0 < hr && hr < 1) ? (1.2 * sig) * (1 - sig) : 0
+ *   soft:  r = b + h;  c = clamp(r, lo, hi);  y = (c - z) * s;  m = (lo <= r && r <= hi)
+ *   hard:  the same with h = (V >= 0) ? 1 : 0          (ties up, a NaN V gives 0)
+ *   f64 from the fp32 h:  u = |2h - 1|;  R = sum(1 - pow(u, beta));
+ *                         dR/dh = (-2 beta * sign(2h - 1)) * pow(u, beta - 1), 0 where u == 0
+ *   grad_V = fp32((((double)g * (double)s) * m + lambda * dR/dh) * (double)hp)   rounded once
+ * pow(1, e) is taken as 1 without a call.  A NaN w gives a NaN y (and m = 0); V is the only
+ * learnable input: no grad_w, s and z are constants.
+ *
+ * vsiq_adaround_fwd_f32: y nullable (then w, scale may be NULL: only R is computed);
+ * hard != 0 selects the hard rounding; reg_out (nullable, device f64[1]) receives R for
+ * `beta` and then needs ws (vsiq_adaround_workspace_doubles(rows, rowlen) doubles) and
+ * `counter` (VSIQ_COUNTER_WORDS words, all 0 before and after) -- per-workgroup records and
+ * one fold by the last workgroup to arrive, no host sync; R's summation order is fixed for
+ * a shape.  VSIQ_E_ARG: rows < 0, rowlen <= 0, qmin > qmax, nq not 1 or rows, a null among
+ * the tensors in use, y and reg_out both NULL, reg_out with hard != 0 or beta <= 0 or
+ * without ws / counter, more than 2^31 - 1 workgroups; VSIQ_E_WS: ws_len too small.
+ * rows == 0 returns 0.  vsiq_adaround_bwd_f32: same checks (beta > 0, lambda not NaN).
+ * Both capture into a HIP graph.  The host twins take HOST pointers and run the same
+ * element functions (csrc/k_adaround.cuh); `mask` (nullable, one byte per element) is m.
+ */
+int64_t vsiq_adaround_workspace_doubles(int64_t rows, int64_t rowlen);
+int vsiq_adaround_fwd_f32(const float *w, const float *v, float *y, int64_t rows, int64_t rowlen,
+                          const double *scale, const double *zp, int64_t nq, int zp_round, int qmin, int qmax,
+                          int hard, double beta, double *reg_out, double *ws, int64_t ws_len, uint32_t *counter,
+                          void *stream);
+int vsiq_adaround_bwd_f32(const float *g, const float *w, const float *v, float *grad_v, int64_t rows,
+                          int64_t rowlen, const double *scale, const double *zp, int64_t nq, int zp_round, int qmin,
+                          int qmax, double lam, double beta, void *stream);
+int vsiq_host_adaround_fwd_f32(const float *w, const float *v, float *y, uint8_t *mask, int64_t rows, int64_t rowlen,
+                               const double *scale, const double *zp, int64_t nq, int zp_round, int qmin, int qmax,
+                               int hard, double beta, double *reg_out);
+int vsiq_host_adaround_bwd_f32(const float *g, const float *w, const float *v, float *grad_v, int64_t rows,
+                               int64_t rowlen, const double *scale, const double *zp, int64_t nq, int zp_round,
+                               int qmin, int qmax, double lam, double beta);
+
+/*
  * BatchNorm folding (modules/fused.py:100-108, :294-300), fp32, reference order:
  *   f = gamma / sqrt(running_var + eps);  w_out[r,:] = w[r,:] * f[r]
  *   b_out[r] = beta[r] + (b[r] - running_mean[r]) * f[r]      (b NULL: 0; b_out nullable)

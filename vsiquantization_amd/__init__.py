@@ -36,6 +36,9 @@ from .quantizers.foreach import enable_multi_tensor_weights, quantize_weights_mu
 from .quantizers.deferred import bundle_qparams, enable_deferred_qparam_grads  # noqa: F401
 from .fakequant import PackedTensor, quantize_pack, unpack_dequant  # noqa: F401
 from .utils.export import export_packed_state, packed_state_weights  # noqa: F401
+from .fakequant import adaround_backward, adaround_forward  # noqa: F401
+from .quantizers.adaround import AdaRoundWeight  # noqa: F401
+from .utils.adaround import adaround_layer, adaround_model  # noqa: F401
 from .utils.quantize_manager import (disable_model_launches, enable_model_launches,  # noqa: F401
                                      model_launches_enabled)
 

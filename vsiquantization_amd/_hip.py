@@ -271,6 +271,15 @@ _SIGS = {
     "vsiq_unpack_dequant": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_int, c_int, c_p], c_int),
     "vsiq_host_quantize_pack_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_int], c_int),
     "vsiq_host_unpack_dequant_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_int, c_int], c_int),
+    "vsiq_adaround_workspace_doubles": ([c_i64, c_i64], c_i64),
+    "vsiq_adaround_fwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_int, c_d, c_p,
+                               c_p, c_i64, c_p, c_p], c_int),
+    "vsiq_adaround_bwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_d, c_d,
+                               c_p], c_int),
+    "vsiq_host_adaround_fwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_int,
+                                    c_d, c_p], c_int),
+    "vsiq_host_adaround_bwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_d,
+                                    c_d], c_int),
 }
 EXPORTED = tuple(_SIGS)
 

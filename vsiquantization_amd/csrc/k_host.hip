@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "host_simd.h"
+#include "k_adaround.cuh"
 #include "k_observe_hist.cuh"
 #include "k_observe_mse.cuh"
 #include "mean_cascade.cuh"
@@ -869,6 +870,79 @@ int vsiq_host_unpack_dequant_f32(const void *packed, float *y, void *codes, int6
       if (y) y[r * rowlen + e] = ((float)q - z) * s;
       if (cd) cd[r * rowlen + e] = (uint8_t)(q & 0xff);
     }
+  });
+  return 0;
+}
+
+}  // extern "C"
+
+// AdaRound on the host (vsiq_adaround_fwd_f32 / vsiq_adaround_bwd_f32; statement in vsiq.h):
+// the element functions of k_adaround.cuh over the flat [rows * rowlen] range in fixed 64K
+// chunks; the regulariser adds each chunk's terms in element order and the chunks in chunk
+// order, so R does not depend on the thread count.  f(e, row qparams) per element.
+namespace vsiq {
+namespace host {
+
+template <class F>
+void ada_chunks(int64_t rows, int64_t rowlen, const double *scale, const double *zp, int64_t nq, int zp_round,
+                int qmin, int qmax, F &&f) {
+  auto qp = [&](int64_t r) {
+    const int64_t c = nq == 1 ? 0 : r;
+    return scale ? make_hqp(scale[c], zp ? zp[c] : 0.0, zp_round, qmin, qmax) : HQP{1.0f, 0.0f, 0.0f, 0.0f};
+  };
+  for_chunks(rows * rowlen, [&](int64_t c, int64_t b, int64_t e1) {
+    int64_t r = b / rowlen, col = b - r * rowlen;
+    HQP p = qp(r);
+    for (int64_t e = b; e < e1; ++e) {
+      f(c, e, p);
+      if (++col == rowlen && e + 1 < e1) {
+        col = 0;
+        p = qp(++r);
+      }
+    }
+  });
+}
+
+}  // namespace host
+}  // namespace vsiq
+
+extern "C" {
+
+int vsiq_host_adaround_fwd_f32(const float *w, const float *v, float *y, uint8_t *mask, int64_t rows, int64_t rowlen,
+                               const double *scale, const double *zp, int64_t nq, int zp_round, int qmin, int qmax,
+                               int hard, double beta, double *reg_out) {
+  if (rows < 0 || rowlen <= 0 || qmin > qmax) return VSIQ_E_ARG;
+  if (rows > 0 && nq != 1 && nq != rows) return VSIQ_E_ARG;
+  if (rows == 0) return 0;
+  if (!v || (!y && !reg_out) || (y && (!w || !scale)) || (mask && !y)) return VSIQ_E_ARG;
+  if (reg_out && (hard || !(beta > 0.0))) return VSIQ_E_ARG;
+  std::vector<double> part(reg_out ? (size_t)cdiv(rows * rowlen, kChunk) : 0, 0.0);
+  ada_chunks(rows, rowlen, y ? scale : nullptr, zp, nq, zp_round, qmin, qmax, [&](int64_t c, int64_t e, const HQP &p) {
+    const float h = hard ? ada_hard(v[e]) : ada_soft(v[e]).h;
+    if (reg_out) part[(size_t)c] += ada_reg(h, beta);
+    if (y) {
+      const AdaOut o = ada_out(w[e] / p.s + p.z, h, p.s, p.z, p.lo, p.hi);
+      y[e] = o.y;
+      if (mask) mask[e] = o.m;
+    }
+  });
+  if (reg_out) {
+    double r = 0.0;
+    for (double t : part) r += t;
+    *reg_out = r;
+  }
+  return 0;
+}
+
+int vsiq_host_adaround_bwd_f32(const float *g, const float *w, const float *v, float *grad_v, int64_t rows,
+                               int64_t rowlen, const double *scale, const double *zp, int64_t nq, int zp_round,
+                               int qmin, int qmax, double lam, double beta) {
+  if (rows < 0 || rowlen <= 0 || qmin > qmax) return VSIQ_E_ARG;
+  if (rows > 0 && nq != 1 && nq != rows) return VSIQ_E_ARG;
+  if (rows == 0) return 0;
+  if (!g || !w || !v || !grad_v || !scale || !(beta > 0.0) || lam != lam) return VSIQ_E_ARG;
+  ada_chunks(rows, rowlen, scale, zp, nq, zp_round, qmin, qmax, [&](int64_t, int64_t e, const HQP &p) {
+    grad_v[e] = ada_grad(g[e], w[e] / p.s + p.z, v[e], p.s, p.z, p.lo, p.hi, lam, beta);
   });
   return 0;
 }

@@ -1217,3 +1217,121 @@ def unpack_dequant(p: PackedTensor, dtype=torch.float32, want_codes: bool = Fals
                                      _i64(qparams.shape[0]), p.qmin, p.bits, H._DT_CODES[dtype], H.stream_of(dev))
     H.check(rc, "vsiq_unpack_dequant")
     return (y, codes) if want_codes else y
+
+
+# --------------------------------------------------------------------------- AdaRound
+def _ada_tensor(t, what, like=None):
+    """A contiguous float32 tensor (CPU or CUDA) of ``like``'s shape and device."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what} must be a torch.Tensor, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what}: only float32 is supported by the HIP fake-quant path, got {t.dtype}")
+    if t.device.type not in ("cpu", "cuda"):
+        raise H.VsiqError(f"{what} is on {t.device}: AdaRound runs on MI355X (HIP) or on CPU tensors")
+    if like is not None:
+        if tuple(t.shape) != tuple(like.shape):
+            raise ValueError(f"{what} must be float32 {tuple(like.shape)} like w, got {tuple(t.shape)}")
+        if t.device != like.device:
+            raise ValueError(f"{what} is on {t.device}, w on {like.device}")
+    return t.detach().contiguous()
+
+
+def _ada_qparams(w, scale, zero_point, axis):
+    """(rows, rowlen, nq, f64 scale, f64 zp | None) of an AdaRound call, the pack entries' rules."""
+    if axis not in (None, 0):
+        raise ValueError(f"adaround: axis must be 0 or None, got {axis!r}")
+    rows, rowlen = _pack_view(w.shape, axis)
+    dev = w.device
+    if axis == 0:
+        as_t = lambda v: v if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
+        s = _per_channel_f64(as_t(scale), rows, dev, "scale")
+        z = _per_channel_f64(as_t(zero_point), rows, dev, "zero point") if zero_point is not None else None
+        return rows, rowlen, rows, s, z
+    s = _pack_scalar_f64(scale, dev)
+    z = _pack_scalar_f64(zero_point, dev) if zero_point is not None else None
+    return rows, rowlen, 1, s, z
+
+
+def adaround_forward(w, V, scale, zero_point, qmin: int, qmax: int, *, axis=None, hard: bool = False,
+                     beta=None, zp_round: bool = False, want_y: bool = True):
+    """AdaRound's forward (include/vsiq.h, "AdaRound"): y = (clamp(floor(w/s + z) + h(V)) - z) * s
+    with the rectified sigmoid h (soft) or h = (V >= 0) (hard), in one launch and one read of
+    w and V.  ``beta`` given: also the f64 regulariser R = sum(1 - |2h - 1|^beta) as a 0-dim
+    tensor on w's device (no host sync).  axis=None: scalar qparams; axis=0: [C] qparams
+    (zero_point None = 0).  Returns (y | None, R | None); want_y=False computes R alone.
+    fp32 only; a CPU tensor takes the native host loops."""
+    w = _ada_tensor(w, "w")
+    V = _ada_tensor(V, "V", w)
+    if not want_y and beta is None:
+        raise ValueError("adaround_forward: nothing to compute (want_y=False and no beta)")
+    if hard and beta is not None:
+        raise ValueError("adaround_forward: the regulariser belongs to the soft forward (hard=True with beta)")
+    rows, rowlen, nq, s, z = _ada_qparams(w, scale, zero_point, axis)
+    dev = w.device
+    y = torch.empty_like(w) if want_y else None
+    reg = torch.empty((), dtype=torch.float64, device=dev) if beta is not None else None
+    b = float(beta) if beta is not None else 1.0
+    if dev.type == "cpu":
+        rc = H.lib().vsiq_host_adaround_fwd_f32(H.ptr(w), H.ptr(V), H.ptr(y), None, _i64(rows), _i64(rowlen),
+                                                H.ptr(s), H.ptr(z), _i64(nq), int(bool(zp_round)), int(qmin),
+                                                int(qmax), int(bool(hard)), b, H.ptr(reg))
+        H.check(rc, "vsiq_host_adaround_fwd_f32")
+        return y, reg
+    ws = wsl = cnt = None
+    if reg is not None:
+        need = int(H.lib().vsiq_adaround_workspace_doubles(_i64(rows), _i64(rowlen)))
+        if need < 0:
+            H.check(need, "vsiq_adaround_workspace_doubles")
+        wk = H.workspace(dev).reserve_doubles(need)
+        ws, wsl, cnt = wk.ws, wk.ws_len, wk.counter
+    rc = H.lib().vsiq_adaround_fwd_f32(H.ptr(w), H.ptr(V), H.ptr(y), _i64(rows), _i64(rowlen), H.ptr(s), H.ptr(z),
+                                       _i64(nq), int(bool(zp_round)), int(qmin), int(qmax), int(bool(hard)), b,
+                                       H.ptr(reg), H.ptr(ws), _i64(wsl or 0), H.ptr(cnt), H.stream_of(dev))
+    H.check(rc, "vsiq_adaround_fwd_f32")
+    return y, reg
+
+
+def adaround_backward(g, w, V, scale, zero_point, qmin: int, qmax: int, *, axis=None, lam: float = 0.0,
+                      beta: float = 2.0, zp_round: bool = False):
+    """grad_V of the soft forward plus lam * R(beta) in one launch:
+    fp32((g * s * m + lam * dR/dh) * h'(V)) per element (include/vsiq.h, "AdaRound")."""
+    w = _ada_tensor(w, "w")
+    V = _ada_tensor(V, "V", w)
+    g = _ada_tensor(g, "grad_output", w)
+    rows, rowlen, nq, s, z = _ada_qparams(w, scale, zero_point, axis)
+    dev = w.device
+    gv = torch.empty_like(V)
+    if dev.type == "cpu":
+        rc = H.lib().vsiq_host_adaround_bwd_f32(H.ptr(g), H.ptr(w), H.ptr(V), H.ptr(gv), _i64(rows), _i64(rowlen),
+                                                H.ptr(s), H.ptr(z), _i64(nq), int(bool(zp_round)), int(qmin),
+                                                int(qmax), float(lam), float(beta))
+        H.check(rc, "vsiq_host_adaround_bwd_f32")
+        return gv
+    rc = H.lib().vsiq_adaround_bwd_f32(H.ptr(g), H.ptr(w), H.ptr(V), H.ptr(gv), _i64(rows), _i64(rowlen), H.ptr(s),
+                                       H.ptr(z), _i64(nq), int(bool(zp_round)), int(qmin), int(qmax), float(lam),
+                                       float(beta), H.stream_of(dev))
+    H.check(rc, "vsiq_adaround_bwd_f32")
+    return gv
+
+
+class AdaRoundFn(torch.autograd.Function):
+    """(y, R) = soft AdaRound forward of (V; w, qparams); V is the only differentiable input.
+    The loss is taken as L(y) + lam * R: backward returns dL/dy's chain through y PLUS
+    lam * dR/dV from the same launch, so R itself is returned non-differentiable (for
+    logging) and must not be added to the loss a second time."""
+
+    @staticmethod
+    def forward(ctx, V, w, scale, zero_point, qmin, qmax, axis, lam, beta, zp_round):
+        y, reg = adaround_forward(w, V, scale, zero_point, qmin, qmax, axis=axis, beta=beta, zp_round=zp_round)
+        ctx.save_for_backward(V, w)
+        ctx.args = (scale, zero_point, qmin, qmax, axis, float(lam), float(beta), zp_round)
+        ctx.mark_non_differentiable(reg)
+        return y, reg
+
+    @staticmethod
+    def backward(ctx, gy, _greg):
+        V, w = ctx.saved_tensors
+        scale, zero_point, qmin, qmax, axis, lam, beta, zp_round = ctx.args
+        gv = adaround_backward(gy, w, V, scale, zero_point, qmin, qmax, axis=axis, lam=lam, beta=beta,
+                               zp_round=zp_round)
+        return gv, None, None, None, None, None, None, None, None, None

@@ -488,16 +488,23 @@ class QuantizationManager(nn.Module):
         clamped exactly when the quantizer's learnable path would (``learn_args``); a [C]
         scale under a PerChannelUniformQuantizer packs per channel (axis 0)."""
         from ..fakequant import quantize_pack
+        s, z, qmin, qmax, axis, zp_round = self.current_grid(x, "export_packed")
+        return quantize_pack(x.detach(), s, z, qmin, qmax, axis=axis, zp_round=zp_round)
+
+    def current_grid(self, x, what: str = "current_grid"):
+        """(scale, zero_point, qmin, qmax, axis, zp_round) that ``quantize(x)`` in eval applies
+        right now -- export_packed's arguments, also AdaRound's (utils/adaround.py).  Raises
+        like export_packed for an unsupported quantizer or a manager without qparams."""
         from .lsq import LSQQuantizer
         from .uniform import UniformQuantizer
         q = self.quantizer
         if type(q) not in (UniformQuantizer, LSQQuantizer, PerChannelUniformQuantizer):
-            raise NotImplementedError(f"export_packed supports UniformQuantizer, LSQQuantizer and "
+            raise NotImplementedError(f"{what} supports UniformQuantizer, LSQQuantizer and "
                                       f"PerChannelUniformQuantizer, not {type(q).__name__}")
         self._join()
         s, z = self.scale, self.zero_point
         if isinstance(s, int) and not isinstance(s, bool) and s == 1:
-            raise RuntimeError("export_packed: this QuantizationManager has neither observed nor learned its "
+            raise RuntimeError(f"{what}: this QuantizationManager has neither observed nor learned its "
                                "qparams (scale is still 1 as constructed); calibrate or train it first")
         per_channel = (isinstance(q, PerChannelUniformQuantizer)
                        and any(isinstance(v, torch.Tensor) and v.dim() == 1 and v.numel() > 1 for v in (s, z)))
@@ -508,7 +515,7 @@ class QuantizationManager(nn.Module):
             else:
                 _, z, learn_zp = q.learn_args(x, z)
                 zp_round = learn_zp == 1
-        return quantize_pack(x.detach(), s, z, q.qmin, q.qmax, axis=0 if per_channel else None, zp_round=zp_round)
+        return s, z, q.qmin, q.qmax, (0 if per_channel else None), zp_round
 
     def _observe_deferred_act(self, x, act):
         """A fused layer's deferred calibration call (calibrate_qat_model's default mode):
