@@ -22,6 +22,7 @@ from vsiquantization_amd import fakequant as FQ
 from vsiquantization_amd.quantizers.deferred import lsq_backward_part
 from oracle import fakequant_np as O
 from tests import goldens as G
+from tests.tuning_common import tuned
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -73,22 +74,6 @@ def cached(key, fn):
     if key not in _want:
         _want[key] = fn()
     return _want[key]
-
-
-def tuned(**knobs):
-    """Context manager: set tuning keys (TUNE_<NAME>=value), restore the defaults after."""
-    defaults = {"NONTEMPORAL": 1, "OBS_KERNEL": 0, "LSQ_GROUPS": 0, "PC_PACKED": 1, "K2O_FORM": 0, "K2O_GROUPS": 0,
-                "K2O_BLOCK": 0}
-
-    class _T:
-        def __enter__(self):
-            for k, v in knobs.items():
-                H.set_tuning(getattr(H, "TUNE_" + k), v)
-
-        def __exit__(self, *exc):
-            for k in knobs:
-                H.set_tuning(getattr(H, "TUNE_" + k), defaults[k])
-    return _T()
 
 
 def host_observe(n, lay, act):
