@@ -9,6 +9,7 @@ import torch
 
 import vsiquantization_amd as V
 from vsiquantization_amd import _hip as H
+from vsiquantization_amd import fakequant as FQ
 from vsiquantization_amd import host
 from oracle import fakequant_np as O
 from tests import goldens as G
@@ -110,7 +111,7 @@ def test_golden_act_fq(case):
         if case["mode"] == "observe":
             qp, _ = host.observe_tensor(c.detach(), symmetric=case["sym"], act=case["act"])
             assert (qp[H.QP_SCALE].item(), qp[H.QP_ZP].item()) == (case["scale"], case["zp"])
-            y = host.fake_quant_fixed(c, None, None, q.qmin, q.qmax, qp=qp, act=case["act"])
+            y = FQ.fake_quant_fixed(c, None, None, q.qmin, q.qmax, qp=qp, act=case["act"])
         elif case["mode"] == "fixed":
             y = q.quantize(c, case["scale"], case["zp"], False, act=case["act"])
         else:
@@ -306,7 +307,7 @@ def test_golden_lsq_fake_quantize_on_cpu(case):
 @pytest.mark.parametrize("shape,axis", [((6, 3, 7, 5), 1), ((2, 5, 7), 1), ((3, 5), 1), ((1, 4, 70000), 1),
                                         ((9, 16, 4, 4), 1), ((12, 27), 0), ((3, 70000), 0)])
 def test_pc_lsq_host_vs_oracle(shape, axis):
-    """host.PcLearnFn on either axis vs the oracle's pc_lsq_forward_backward: y / grad_x
+    """PerChannelLearnFn on CPU tensors, either axis, vs the oracle's pc_lsq_forward_backward: y / grad_x
     bitwise, f64 [C] gradients <= 1e-9 of the oracle's (f64 sums in another order)."""
     rng = np.random.default_rng(sum(shape) + axis)
     x = (rng.standard_normal(shape) * 2).astype(np.float32)
@@ -318,7 +319,7 @@ def test_pc_lsq_host_vs_oracle(shape, axis):
     sp = torch.nn.Parameter(torch.tensor(s, dtype=torch.float64))
     zp = torch.nn.Parameter(torch.tensor(z, dtype=torch.float64))
     xg = t(x, grad=True)
-    y = host.PcLearnFn.apply(xg, sp, zp, 0, 255, gscale, True, axis)
+    y = FQ.PerChannelLearnFn.apply(xg, sp, zp, 0, 255, gscale, True, axis)
     y.backward(t(g))
     yo, gxo, gso, gzo = O.pc_lsq_forward_backward(x, g, s, z, 0, 255, gscale, axis=axis)
     G.assert_bitwise_f32(npy(y), yo, "y")

@@ -112,7 +112,7 @@ def test_host_loop_equals_oracle(qc):
 @pytest.mark.parametrize("shape,axis", [((6, 5, 3, 3), 0), ((4, LONG), 0), ((3, 7, 4), 1), ((2, 4, LONG), 1)])
 @pytest.mark.parametrize("learn_zp", [False, True])
 def test_host_per_channel_loops_equal_oracle(shape, axis, learn_zp):
-    """vsiq_host_pc_lsq_bwd_f32 / vsiq_host_pcm_lsq_bwd_f32 (PcLearnFn, axis 0 and 1) with
+    """vsiq_host_pc_lsq_bwd_f32 / vsiq_host_pcm_lsq_bwd_f32 (PerChannelLearnFn on CPU, axis 0 / 1) with
     the three special channels, rows below and above the host loops' chunk."""
     sym = not learn_zp
     qmin, qmax = O.qrange(4, sym)
@@ -121,7 +121,7 @@ def test_host_per_channel_loops_equal_oracle(shape, axis, learn_zp):
     exp = EC.pc_oracle(x, g, s, z, qmin, qmax, gscale, axis, learn_zp)
     sp, zp = t(s, grad=True), t(z, grad=learn_zp)
     xg = t(x, grad=True)
-    y = host.PcLearnFn.apply(xg, sp, zp, qmin, qmax, gscale, learn_zp, axis)
+    y = FQ.PerChannelLearnFn.apply(xg, sp, zp, qmin, qmax, gscale, learn_zp, axis)
     y.backward(t(g))
     EC.check(y.detach().numpy(), xg.grad.numpy(), sp.grad.numpy(), zp.grad.numpy() if learn_zp else None, exp,
              f"{shape} axis {axis}", zp_grad=learn_zp)
@@ -137,6 +137,6 @@ def test_host_lsq_fake_quantize_edge_fixture():
     sp, zp = t(G.arr(case["scale"]).copy(), grad=True), t(G.arr(case["zp"]).copy(), grad=True)
     gsc = O.lsq_module_grad_scale(x.shape, case["qmax"], True, case["config_act"])
     xg = t(x, grad=True)
-    y = host.PcLearnFn.apply(xg, sp, zp, case["qmin"], case["qmax"], gsc, True, 1)
+    y = FQ.PerChannelLearnFn.apply(xg, sp, zp, case["qmin"], case["qmax"], gsc, True, 1)
     y.backward(t(g))
     EC.check_golden(y.detach().numpy(), xg.grad.numpy(), sp.grad.numpy(), zp.grad.numpy(), case, case["key"])

@@ -13,7 +13,7 @@ from tests.pc_mse_common import (FAMILIES, ONGRID_RATIOS, OracleState, check_aga
                                  same_bits)
 from vsiquantization_amd import _hip as H
 from vsiquantization_amd import host
-from vsiquantization_amd.fakequant import per_channel_observe_mse
+from vsiquantization_amd.fakequant import PerChannelFQFn, per_channel_observe_mse
 from vsiquantization_amd.observers import PerChannelMinMaxObserver, PerChannelMSEObserver
 from vsiquantization_amd.utils.registry import CLASS_REGISTRY
 
@@ -181,7 +181,7 @@ def test_manager_routes_and_observer_state():
     y.backward(torch.ones_like(y))
     s, z = qm.observer.get_scale_zero_point()
     ref = w.clone().requires_grad_(True)
-    yr = host.PcFixedFn.apply(ref, s, z, qm.quantizer.qmin, qm.quantizer.qmax)
+    yr = PerChannelFQFn.apply(ref, s, z, qm.quantizer.qmin, qm.quantizer.qmax)
     yr.backward(torch.ones_like(yr))
     assert same_bits(y, yr) and same_bits(wg.grad, ref.grad)
     import copy

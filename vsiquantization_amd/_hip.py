@@ -430,6 +430,40 @@ def mask_buffer(rows: int, rowlen: int, device) -> torch.Tensor:
     return torch.empty(max(words, 1), dtype=torch.int64, device=device)
 
 
+def codes_buffer(shape, qmin: int, device) -> torch.Tensor:
+    """Storage of the integer codes of a grid that starts at qmin: int8 (qmin < 0) or uint8."""
+    return torch.empty(shape, dtype=torch.int8 if qmin < 0 else torch.uint8, device=device)
+
+
+def qden(symmetric: bool, num_bits: int, eps: float) -> float:
+    """Denominator of minmax.py:72 / :75, evaluated with Python floats like the reference."""
+    return (2 ** (num_bits - 1) - 1 + eps) if symmetric else (2 ** num_bits - 1 + eps)
+
+
+def empty_error() -> RuntimeError:
+    """What torch's min() raises on an empty tensor (minmax.py:42-43): every observer's error."""
+    return RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+
+
+def pc_observe_buffers(x: torch.Tensor, C: int, run_min, run_max, quantize: bool, want_row_stats: bool):
+    """What a per-channel observe of x ([C, ...]) works on, on x's device: the running state
+    (fresh 0/0 where none is given: minmax.py:28-29, one fill; ValueError at another channel
+    count) and its outputs (run_min, run_max, y | None, scale f64[C], zp f64[C], row_stats
+    f64[C, 3] | None)."""
+    dev = x.device
+    if run_min is None or run_max is None:
+        state = torch.zeros(2, C, dtype=torch.float32, device=dev)
+        run_min = state[0] if run_min is None else run_min
+        run_max = state[1] if run_max is None else run_max
+    if run_min.numel() != C or run_max.numel() != C:
+        raise ValueError(f"running state has {run_min.numel()} / {run_max.numel()} channels, tensor has {C}")
+    y = torch.empty_like(x) if quantize else None
+    scale = torch.empty(C, dtype=torch.float64, device=dev)
+    zp = torch.empty(C, dtype=torch.float64, device=dev)
+    rstats = torch.empty(C, 3, dtype=torch.float64, device=dev) if want_row_stats else None
+    return run_min, run_max, y, scale, zp, rstats
+
+
 def set_tuning(key: int, value: int):
     check(lib().vsiq_set_tuning(int(key), int(value)), "vsiq_set_tuning")
 

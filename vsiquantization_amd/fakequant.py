@@ -1,5 +1,8 @@
 """torch-facing fake-quant ops over the HIP C ABI (CPU tensors: the native host loops of
-host.py, never the oracle).
+host.py, never the oracle).  This is the one module that chooses between the two: an op
+with a host counterpart tests ``_host.is_host(x)`` (a CPU float32 tensor) first and hands
+the call to host.py's plain function of that op, so the autograd Functions here serve both
+sides and callers never branch on the device.
 
 Each op here is one (or two) kernel launches on the tensor's current HIP
 stream, no host synchronisation, and is the MI355X replacement of one chain of
@@ -29,14 +32,10 @@ import torch
 
 from . import _hip as H
 from . import host as _host
+from ._hip import qden   # re-exported: the observers and distributed.py import it from here
 
 
 # --------------------------------------------------------------------------- scalars
-def qden(symmetric: bool, num_bits: int, eps: float) -> float:
-    """Denominator of minmax.py:72 / :75, evaluated with Python floats like the reference."""
-    return (2 ** (num_bits - 1) - 1 + eps) if symmetric else (2 ** num_bits - 1 + eps)
-
-
 def _as_f64_device(t: torch.Tensor, device) -> torch.Tensor:
     t = t.detach()
     if t.numel() != 1:
@@ -85,9 +84,7 @@ def fake_quant(x: torch.Tensor, scale, zero_point, qmin: int, qmax: int, *, zp_r
     dev = x.device
     y = torch.empty_like(x)
     mask = H.mask_buffer(1, x.numel(), dev) if want_mask else None
-    codes = None
-    if want_codes:
-        codes = torch.empty(x.shape, dtype=torch.int8 if qmin < 0 else torch.uint8, device=dev)
+    codes = H.codes_buffer(x.shape, qmin, dev) if want_codes else None
     if qp is not None:
         sd, sh, zd, zh = None, 0.0, None, 0.0
     else:
@@ -105,7 +102,11 @@ def ste_backward(g: torch.Tensor, mask: torch.Tensor, scale, rowlen: int = 0, *,
                  act=None) -> torch.Tensor:
     """gx = (mask ? g*s : 0) / s  — autograd of uniform.py:55,95 with a fixed scale;
     with ``act``, the activation's backward at the pre-activation ``pre`` follows.
-    bfloat16 / float16 g (per-tensor form only; ``pre`` of g's dtype): fake_quant's rule."""
+    bfloat16 / float16 g (per-tensor form only; ``pre`` of g's dtype): fake_quant's rule.
+    A CPU g: the host loop, per-tensor form (per row: pc_ste_backward); mask as host.fake_quant
+    wrote it."""
+    if _host.is_host(g):
+        return _host.ste_backward(g, mask, scale, pre=pre, act=act)
     g, dt = H.require_device_float(g, "grad_output")
     a = H.act_code(act)
     if a != H.ACT_NONE:
@@ -165,6 +166,13 @@ def activation(x, act):
     return torch.nn.functional.relu(x) if act == "relu" else torch.nn.functional.silu(x)
 
 
+def _ste_grad(ctx, gy):
+    """grad_x of a per-tensor Function that saved (mask[, pre-activation]) and set ctx.scale / ctx.act."""
+    saved = ctx.saved_tensors
+    pre = saved[1] if len(saved) > 1 else None
+    return ste_backward(gy.contiguous(), saved[0], ctx.scale, pre=pre, act=ctx.act)
+
+
 class FakeQuantFixedFn(torch.autograd.Function):
     """Fixed-qparam fake quant with the reference's STE gradient (x only)."""
 
@@ -185,12 +193,9 @@ class FakeQuantFixedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        saved = ctx.saved_tensors
-        pre = saved[1] if len(saved) > 1 else None
         if gy.dtype != ctx.dtype:
             raise TypeError(f"grad_output is {gy.dtype}, the fake-quantized tensor was {ctx.dtype}")
-        gx = ste_backward(gy.contiguous(), saved[0], ctx.scale, pre=pre, act=ctx.act)
-        return gx, None, None, None, None, None, None
+        return _ste_grad(ctx, gy), None, None, None, None, None, None
 
 
 def _is_half(x) -> bool:
@@ -215,10 +220,9 @@ def fake_quant_fixed(x, scale, zero_point, qmin, qmax, qp=None, act=None):
     (C++ node of _vsiq_torch.so, or FakeQuantFixedFn with VSIQ_TORCH_EXT=0; the C++ nodes
     are fp32-only, so a bfloat16 / float16 x always takes FakeQuantFixedFn).  CPU tensors:
     the native host path (host.py)."""
-    if _host.is_host(x):
-        return _host.fake_quant_fixed(x, scale, zero_point, qmin, qmax, qp=qp, act=act)
+    host = _host.is_host(x)   # never the C++ node: FakeQuantFixedFn's fake_quant / ste_backward take the host loops
     if x.requires_grad and torch.is_grad_enabled():
-        if H.torch_ext_enabled() and not _is_half(x):
+        if H.torch_ext_enabled() and not host and not _is_half(x):
             x = H.require_device_f32(x)
             st, sh = _qarg(scale) if qp is None else (None, 0.0)
             zt, zh = _qarg(zero_point) if qp is None else (None, 0.0)
@@ -231,10 +235,9 @@ def fake_quant_learn(x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=Non
     """Learnable fake quant (uniform.py:47-56): K1/K5 forward, K4 backward with the
     ScaleGradient factor ``gscale`` (C++ node of _vsiq_torch.so, or FakeQuantLearnFn
     with VSIQ_TORCH_EXT=0 or a bfloat16 / float16 x).  CPU tensors: the native host path
-    (host.py)."""
-    if _host.is_host(x):
-        return _host.fake_quant_learn(x, scale, zero_point, qmin, qmax, gscale, learn_zp, act)
-    if H.torch_ext_enabled() and learn_zp != 2 and not _is_half(x):   # the C++ node takes its K4 workspace from its own cache
+    (host.py: FakeQuantLearnFn's fake_quant / lsq_backward take the host loops)."""
+    # the C++ node takes its K4 workspace from its own cache
+    if H.torch_ext_enabled() and learn_zp != 2 and not _host.is_host(x) and not _is_half(x):
         x = H.require_device_f32(x)
         st, sh = _qarg(scale)
         zt, zh = _qarg(zero_point)
@@ -248,7 +251,9 @@ def lsq_backward(g, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None
     """K4: (grad_x, f64[2] {grad_scale, grad_zp}); with ``act``, x is the pre-activation
     and grad_x goes through the activation's backward.  bfloat16 / float16 g and x (the
     same dtype): fake_quant's rule; the f64 gradients are the fp32 call's on the widened
-    tensors, bit for bit."""
+    tensors, bit for bit.  A CPU g: the host loop."""
+    if _host.is_host(g):
+        return _host.lsq_backward(g, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act)
     g, dt = H.require_device_float(g, "grad_output")
     x = H.require_same_dtype(x, g, "x")
     dev = g.device
@@ -265,6 +270,14 @@ def lsq_backward(g, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None
     return gx, grads
 
 
+def _qparam_grad(g, v, needed):
+    """The f64 gradient g of the scale / zero-point input v as autograd takes it: on v's
+    device, in v's dtype and shape; None where v is no tensor or its gradient is not needed."""
+    if needed and isinstance(v, torch.Tensor):
+        return g.to(device=v.device, dtype=v.dtype).reshape(v.shape)
+    return None
+
+
 class FakeQuantLearnFn(torch.autograd.Function):
     """Learnable-scale (and, asymmetric, learnable zero-point) fake quant.
 
@@ -273,9 +286,8 @@ class FakeQuantLearnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None):
-        x, _ = H.require_device_float(x)
-        y, _, _ = fake_quant(x, scale, zero_point, qmin, qmax, zp_round=learn_zp == 1, act=act)
-        ctx.save_for_backward(x)
+        y, _, _ = fake_quant(x, scale, zero_point, qmin, qmax, zp_round=learn_zp == 1, act=act)   # checks x
+        ctx.save_for_backward(x.contiguous())
         ctx.scale, ctx.zp = scale, zero_point
         ctx.args = (qmin, qmax, gscale, learn_zp, act)
         return y
@@ -288,11 +300,8 @@ class FakeQuantLearnFn(torch.autograd.Function):
         if gy.dtype != x.dtype:
             raise TypeError(f"grad_output is {gy.dtype}, the fake-quantized tensor was {x.dtype}")
         gx, grads = lsq_backward(gy.contiguous(), x, s, z, qmin, qmax, gscale, learn_zp, act=act)
-        gs = gz = None
-        if isinstance(s, torch.Tensor) and ctx.needs_input_grad[1]:
-            gs = grads[0].to(device=s.device, dtype=s.dtype).reshape(s.shape)
-        if learn_zp and isinstance(z, torch.Tensor) and ctx.needs_input_grad[2]:
-            gz = grads[1].to(device=z.device, dtype=z.dtype).reshape(z.shape)
+        gs = _qparam_grad(grads[0], s, ctx.needs_input_grad[1])
+        gz = _qparam_grad(grads[1], z, learn_zp and ctx.needs_input_grad[2])
         return gx, gs, gz, None, None, None, None, None
 
 
@@ -380,10 +389,7 @@ class FakeQuantLearnMultiFn(torch.autograd.Function):
         for i, sp in enumerate(specs):
             for col, v, learn in ((0, sp.scale, True), (1, sp.zero_point, sp.learn_zp)):
                 if isinstance(v, torch.Tensor) and v.requires_grad:
-                    g = None
-                    if learn and ctx.needs_input_grad[1 + j]:
-                        g = grads[i, col].to(device=v.device, dtype=v.dtype).reshape(v.shape)
-                    out.append(g)
+                    out.append(_qparam_grad(grads[i, col], v, learn and ctx.needs_input_grad[1 + j]))
                     j += 1
         return (None, *gxs, *out)
 
@@ -431,7 +437,7 @@ def observe_tensor(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, eps: 
                                     want_qp=want_qp, want_stats=want_stats, act=act)
     x, dt = H.require_device_float(x)
     if x.numel() == 0:
-        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+        raise H.empty_error()
     dev = x.device
     qp = torch.empty(H.QP_LEN, dtype=torch.float64, device=dev) if want_qp else None
     st = torch.empty(H.ST_LEN, dtype=torch.float64, device=dev) if want_stats else None
@@ -581,22 +587,22 @@ def observe_fake_quant(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, e
     x = H.require_device_f32(x)
     n = x.numel()
     if n == 0:
-        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+        raise H.empty_error()
     dev = x.device
     y = torch.empty_like(x)
     qp = torch.empty(H.QP_LEN, dtype=torch.float64, device=dev)
     st = torch.empty(H.ST_LEN, dtype=torch.float64, device=dev)
     mask = H.mask_buffer(1, n, dev) if want_mask else None
-    codes = torch.empty(x.shape, dtype=torch.int8 if qmin < 0 else torch.uint8, device=dev) if want_codes else None
+    codes = H.codes_buffer(x.shape, qmin, dev) if want_codes else None
     if parts is None:
         parts = n > _K8_ELEMS
+    # the arguments the three entry points share
+    args = (H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(n), H.act_code(act), H.ptr(st), H.ptr(run_minmax),
+            H.ptr(qp), int(bool(symmetric)), qden(symmetric, num_bits, eps), float(eps), int(qmin), int(qmax))
     if parts == "k10":
         w = H.workspace(dev, n)
-        rc = H.lib().vsiq_act_observe_fq_grid_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(n),
-                                                  H.act_code(act), H.ptr(st), H.ptr(run_minmax), H.ptr(qp),
-                                                  int(bool(symmetric)), qden(symmetric, num_bits, eps), float(eps),
-                                                  int(qmin), int(qmax), H.ptr(w.ws), _i64(w.ws_len),
-                                                  H.ptr(w.counter), H.stream_of(dev))
+        rc = H.lib().vsiq_act_observe_fq_grid_f32(*args, H.ptr(w.ws), _i64(w.ws_len), H.ptr(w.counter),
+                                                  H.stream_of(dev))
         H.check(rc, "vsiq_act_observe_fq_grid_f32")
         # a workgroup that timed out at the grid barrier wrote NaN and counted itself: fail
         # loudly (one host sync; K10 is an opt-in measurement path; not checkable while the
@@ -608,17 +614,10 @@ def observe_fake_quant(x: torch.Tensor, *, symmetric: bool, num_bits: int = 8, e
                               "co-resident); the outputs of the timed-out workgroups are NaN")
     elif parts:   # True / "k9"
         w = H.workspace(dev, n)
-        rc = H.lib().vsiq_act_observe_fq_parts_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(n),
-                                                   H.act_code(act), H.ptr(st), H.ptr(run_minmax), H.ptr(qp),
-                                                   int(bool(symmetric)), qden(symmetric, num_bits, eps), float(eps),
-                                                   int(qmin), int(qmax), H.ptr(w.ws), _i64(w.ws_len),
-                                                   H.stream_of(dev))
+        rc = H.lib().vsiq_act_observe_fq_parts_f32(*args, H.ptr(w.ws), _i64(w.ws_len), H.stream_of(dev))
         H.check(rc, "vsiq_act_observe_fq_parts_f32")
     else:
-        rc = H.lib().vsiq_act_observe_fq_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(n),
-                                             H.act_code(act), H.ptr(st), H.ptr(run_minmax), H.ptr(qp),
-                                             int(bool(symmetric)), qden(symmetric, num_bits, eps), float(eps),
-                                             int(qmin), int(qmax), H.stream_of(dev))
+        rc = H.lib().vsiq_act_observe_fq_f32(*args, H.stream_of(dev))
         H.check(rc, "vsiq_act_observe_fq_f32")
     return y, qp, st, mask, codes
 
@@ -639,10 +638,7 @@ class ObserveFakeQuantFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy, _gqp, _gst):
-        saved = ctx.saved_tensors
-        pre = saved[1] if len(saved) > 1 else None
-        gx = ste_backward(gy.contiguous(), saved[0], ctx.scale, pre=pre, act=ctx.act)
-        return gx, None, None, None, None, None, None, None
+        return _ste_grad(ctx, gy), None, None, None, None, None, None, None
 
 
 def part_slot_doubles(n: int | None = None) -> int:
@@ -669,7 +665,7 @@ def observe_parts(x: torch.Tensor, out: torch.Tensor | None = None, act=None) ->
     no running update.  Fold with ``fold_parts``."""
     x = H.require_device_f32(x)
     if x.numel() == 0:
-        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+        raise H.empty_error()
     need = part_slot_doubles(x.numel())
     if out is None:
         out = torch.empty(need, dtype=torch.float64, device=x.device)
@@ -688,7 +684,7 @@ def observe_parts_out(x: torch.Tensor, act, out: torch.Tensor | None = None):
     format, one per workgroup; fold with ``fold_parts``).  Returns (y, out)."""
     x = H.require_device_f32(x)
     if x.numel() == 0:
-        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+        raise H.empty_error()
     need = part_out_slot_doubles(x.numel())
     if out is None:
         out = torch.empty(need, dtype=torch.float64, device=x.device)
@@ -715,7 +711,7 @@ def observe_parts_multi(xs, outs, act=None) -> list:
         if x.device != dev:
             raise ValueError("observe_parts_multi: all tensors must be on one device")
         if x.numel() == 0:
-            raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+            raise H.empty_error()
         out = outs[i] if outs is not None else None
         need = part_slot_doubles(x.numel())
         if out is None:
@@ -759,24 +755,19 @@ def per_channel_observe_fq(x: torch.Tensor, *, symmetric: bool, qmin: int, qmax:
     """Fused per-channel (axis 0) MinMax observe + f64 qparams + fake quant, one pass (K3).
 
     quantize=False observes only (state, qparams, stats; y is None).
-    Returns dict(y, scale f64[C], zp f64[C], run_min, run_max, mask, codes, row_stats f64[C,3])."""
+    Returns dict(y, scale f64[C], zp f64[C], run_min, run_max, mask, codes, row_stats f64[C,3]).
+    A CPU tensor takes the native host loops (host.pc_observe_fq; byte mask, no codes)."""
+    if _host.is_host(x) and not want_codes:
+        return _host.pc_observe_fq(x, symmetric=symmetric, qmin=qmin, qmax=qmax, obs_bits=obs_bits, eps=eps,
+                                   run_min=run_min, run_max=run_max, quantize=quantize, want_mask=want_mask,
+                                   want_row_stats=want_row_stats)
     x = H.require_device_f32(x)
     dev = x.device
     C = x.shape[0] if x.dim() > 0 else 1
     rowlen = x.numel() // max(C, 1)
-    if run_min is None or run_max is None:   # fresh observer state 0/0 (minmax.py:28-29), one fill
-        state = torch.zeros(2, C, dtype=torch.float32, device=dev)
-        run_min = state[0] if run_min is None else run_min
-        run_max = state[1] if run_max is None else run_max
-    if run_min.numel() != C or run_max.numel() != C:
-        raise ValueError(f"running state has {run_min.numel()} channels, tensor has {C}")
-    y = torch.empty_like(x) if quantize else None
-    scale = torch.empty(C, dtype=torch.float64, device=dev)
-    zp = torch.empty(C, dtype=torch.float64, device=dev)
+    run_min, run_max, y, scale, zp, rstats = H.pc_observe_buffers(x, C, run_min, run_max, quantize, want_row_stats)
     mask = H.mask_buffer(C, rowlen, dev) if (want_mask and quantize) else None
-    codes = (torch.empty(x.shape, dtype=torch.int8 if qmin < 0 else torch.uint8, device=dev)
-             if (want_codes and quantize) else None)
-    rstats = torch.empty(C, 3, dtype=torch.float64, device=dev) if want_row_stats else None
+    codes = H.codes_buffer(x.shape, qmin, dev) if (want_codes and quantize) else None
     rc = H.lib().vsiq_pc_observe_fq_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(C),
                                         _i64(rowlen), H.ptr(run_min), H.ptr(run_max), H.ptr(scale),
                                         H.ptr(zp), H.ptr(rstats), int(bool(symmetric)), int(qmin),
@@ -787,30 +778,36 @@ def per_channel_observe_fq(x: torch.Tensor, *, symmetric: bool, qmin: int, qmax:
                 row_stats=rstats)
 
 
+def _mean_layout(ref):
+    """(vec, threads) of the host layout ``ref``: default H.mean_reference(), else this process's threads."""
+    if ref is None:
+        ref = H.mean_reference() or (8, torch.get_num_threads())
+    return int(ref[0]), int(ref[1])
+
+
+def _torch_mean_launch(x, act, layout, out, st, what):
+    """vsiq_torch_mean_f32 of a CUDA fp32 x into ``out`` (fp32[4]) or ``st`` (a stats record),
+    with the workspace its layout needs."""
+    nb = int(H.lib().vsiq_torch_mean_ws_bytes(_i64(x.numel()), *layout))
+    if nb < 0:
+        raise ValueError(f"{what}: unsupported layout {layout} for {x.numel()} elements")
+    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=x.device)
+    rc = H.lib().vsiq_torch_mean_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), *layout, H.ptr(out), H.ptr(st),
+                                     H.ptr(ws), _i64(ws.numel()), H.stream_of(x.device))
+    H.check(rc, "vsiq_torch_mean_f32")
+
+
 def torch_mean(x: torch.Tensor, act=None, ref=None) -> torch.Tensor:
     """K11: fp32[4] {sum|act(x)|, sum act(x), mean|act(x)|, mean act(x)} bit for bit as
     torch's CPU kernel sums them on a host of layout ``ref`` = (vec, threads) (default
     H.mean_reference(), else this process's threads) -- quantization_manager.py:66-67's
     torch.mean(torch.abs(x)) / torch.mean(x).  On x's device (CPU tensors: the host loop)."""
-    if ref is None:
-        ref = H.mean_reference() or (8, torch.get_num_threads())
-    vec, threads = int(ref[0]), int(ref[1])
-    from . import host
-    if host.is_host(x):
-        x = x.contiguous()
-        out = torch.empty(4, dtype=torch.float32)
-        rc = H.lib().vsiq_host_torch_mean_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), vec, threads, H.ptr(out))
-        H.check(rc, "vsiq_host_torch_mean_f32")
-        return out
+    layout = _mean_layout(ref)
+    if _host.is_host(x):
+        return _host.torch_mean(x, act, *layout)
     x = H.require_device_f32(x)
-    nb = int(H.lib().vsiq_torch_mean_ws_bytes(_i64(x.numel()), vec, threads))
-    if nb < 0:
-        raise ValueError(f"torch_mean: unsupported layout {ref} for {x.numel()} elements")
-    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=x.device)
     out = torch.empty(4, dtype=torch.float32, device=x.device)
-    rc = H.lib().vsiq_torch_mean_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), vec, threads, H.ptr(out), None,
-                                     H.ptr(ws), _i64(ws.numel()), H.stream_of(x.device))
-    H.check(rc, "vsiq_torch_mean_f32")
+    _torch_mean_launch(x, act, layout, out, None, "torch_mean")
     return out
 
 
@@ -820,22 +817,12 @@ def torch_stats(x: torch.Tensor, act=None, ref=None) -> torch.Tensor:
     .item()-ed): K11 and its std pass (vsiq_torch_mean_f32 with a stats record), on x's
     device.  CPU tensors: torch_mean's two means and NaN for std (the host observer's
     record holds the host std)."""
-    from . import host
-    if host.is_host(x):
+    if _host.is_host(x):
         m = torch_mean(x, act=act, ref=ref)
         return torch.stack([m[2].double(), m[3].double(), torch.tensor(float("nan"), dtype=torch.float64)])
-    if ref is None:
-        ref = H.mean_reference() or (8, torch.get_num_threads())
-    vec, threads = int(ref[0]), int(ref[1])
     x = H.require_device_f32(x)
-    nb = int(H.lib().vsiq_torch_mean_ws_bytes(_i64(x.numel()), vec, threads))
-    if nb < 0:
-        raise ValueError(f"torch_stats: unsupported layout {ref} for {x.numel()} elements")
-    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=x.device)
     st = torch.empty(H.ST_LEN, dtype=torch.float64, device=x.device)   # the three fields read are all written
-    rc = H.lib().vsiq_torch_mean_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), vec, threads, None, H.ptr(st),
-                                     H.ptr(ws), _i64(ws.numel()), H.stream_of(x.device))
-    H.check(rc, "vsiq_torch_mean_f32")
+    _torch_mean_launch(x, act, _mean_layout(ref), None, st, "torch_stats")
     return st[H.ST_MEANABS:H.ST_STD + 1]
 
 
@@ -862,7 +849,9 @@ def _pc_view(x: torch.Tensor, axis: int):
 
 
 def _per_channel_f64(v, C, dev, what):
-    t = v.detach().to(dev, torch.float64).reshape(-1).contiguous()
+    """v (a [C]-element tensor, or a 1-element tensor / a number: every channel's) as f64 [C] on dev."""
+    v = v.detach() if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64)
+    t = v.to(dev, torch.float64).reshape(-1).contiguous()
     if t.numel() == 1 and C > 1:
         t = t.expand(C).contiguous()
     if t.numel() != C:
@@ -873,14 +862,17 @@ def _per_channel_f64(v, C, dev, what):
 def per_channel_fake_quant(x, scale: torch.Tensor, zp, qmin, qmax, *, zp_round=False,
                            want_mask=False, want_codes=False, axis=0):
     """Per-channel fake quant with given [C] qparams (any float dtype; zp may be None = 0)
-    along ``axis`` 0 ([C, ...] weights) or 1 ([N, C, ...] activations)."""
+    along ``axis`` 0 ([C, ...] weights) or 1 ([N, C, ...] activations).  Returns (y, mask | None,
+    codes | None).  A CPU tensor takes the native host loops (host.pc_fake_quant; byte mask, no codes)."""
+    if _host.is_host(x) and not want_codes:
+        return (*_host.pc_fake_quant(x, scale, zp, qmin, qmax, zp_round=zp_round, want_mask=want_mask, axis=axis),
+                None)
     x = H.require_device_f32(x)
     dev = x.device
     rows, rowlen, C = _pc_view(x, axis)
     y = torch.empty_like(x)
     mask = H.mask_buffer(rows, rowlen, dev) if want_mask else None
-    codes = (torch.empty(x.shape, dtype=torch.int8 if qmin < 0 else torch.uint8, device=dev)
-             if want_codes else None)
+    codes = H.codes_buffer(x.shape, qmin, dev) if want_codes else None
     s = _per_channel_f64(scale, C, dev, "scale")
     z = _per_channel_f64(zp, C, dev, "zero point") if zp is not None else None
     rc = H.lib().vsiq_pcm_fq_fwd_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(rows),
@@ -890,28 +882,39 @@ def per_channel_fake_quant(x, scale: torch.Tensor, zp, qmin, qmax, *, zp_round=F
     return y, mask, codes
 
 
+def pc_ste_backward(g, mask, scale, axis=0):
+    """The per-channel STE backward: row r of g's row view (``axis`` as per_channel_fake_quant)
+    is (mask ? g*s : 0) / s with s = fp32(scale[r % C]); ``mask`` as the forward on g's side
+    wrote it (device: H.mask_buffer's 1-bit words; CPU: one byte per element)."""
+    if _host.is_host(g):
+        return _host.pc_ste_backward(g, mask, scale, axis)
+    rows, rowlen, C = _pc_view(g, axis)
+    s = _per_channel_f64(scale, C, g.device, "scale")
+    if rows != C:   # axis 1: the STE kernel takes one scale per row
+        s = s.repeat(rows // C)
+    return ste_backward(g.contiguous(), mask, s, rowlen)
+
+
 class PerChannelFQFn(torch.autograd.Function):
     """Per-channel fake quant with given [C] qparams and the STE backward."""
 
     @staticmethod
     def forward(ctx, x, scale, zp, qmin, qmax, axis=0):
         y, mask, _ = per_channel_fake_quant(x, scale, zp, qmin, qmax, want_mask=True, axis=axis)
-        rows, rowlen, C = _pc_view(x, axis)
-        s = _per_channel_f64(scale, C, x.device, "scale")
-        if rows != C:   # axis 1: the STE kernel takes one scale per row
-            s = s.repeat(rows // C)
-        ctx.save_for_backward(mask, s)
-        ctx.rowlen = rowlen
+        ctx.save_for_backward(mask, _per_channel_f64(scale, x.shape[axis], x.device, "scale"))
+        ctx.axis = axis
         return y
 
     @staticmethod
     def backward(ctx, gy):
         mask, scale = ctx.saved_tensors
-        return ste_backward(gy.contiguous(), mask, scale, ctx.rowlen), None, None, None, None, None
+        return pc_ste_backward(gy, mask, scale, ctx.axis), None, None, None, None, None
 
 
-def pc_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, axis):
-    """K6: (grad_x, grad_scale f64 [C], grad_zp f64 [C])."""
+def pc_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, axis=0):
+    """K6: (grad_x, grad_scale f64 [C], grad_zp f64 [C]).  A CPU g: the host loops."""
+    if _host.is_host(g):
+        return _host.pc_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, axis)
     g = H.require_device_f32(g, "grad_output")
     dev = g.device
     rows, rowlen, C = _pc_view(x, axis)
@@ -939,10 +942,9 @@ class PerChannelLearnFn(torch.autograd.Function):
     already multiplied by ``gscale`` (ScaleGradient, uniform.py:242-255)."""
 
     @staticmethod
-    def forward(ctx, x, scale, zero_point, qmin, qmax, gscale, learn_zp, axis):
-        x = H.require_device_f32(x)
-        y, _, _ = per_channel_fake_quant(x, scale, zero_point, qmin, qmax, zp_round=learn_zp, axis=axis)
-        ctx.save_for_backward(x)
+    def forward(ctx, x, scale, zero_point, qmin, qmax, gscale, learn_zp, axis=0):
+        y, _, _ = per_channel_fake_quant(x, scale, zero_point, qmin, qmax, zp_round=learn_zp, axis=axis)   # checks x
+        ctx.save_for_backward(x.contiguous())
         ctx.scale, ctx.zp = scale, zero_point
         ctx.args = (qmin, qmax, gscale, learn_zp, axis)
         return y
@@ -953,12 +955,9 @@ class PerChannelLearnFn(torch.autograd.Function):
         qmin, qmax, gscale, learn_zp, axis = ctx.args
         s, z = ctx.scale, ctx.zp
         gx, gs, gz = pc_lsq_backward(gy.contiguous(), x, s, z, qmin, qmax, gscale, learn_zp, axis)
-        out_s = out_z = None
-        if isinstance(s, torch.Tensor) and ctx.needs_input_grad[1]:
-            out_s = gs.to(device=s.device, dtype=s.dtype).reshape(s.shape)
-        if learn_zp and isinstance(z, torch.Tensor) and ctx.needs_input_grad[2]:
-            out_z = gz.to(device=z.device, dtype=z.dtype).reshape(z.shape)
-        return gx, out_s, out_z, None, None, None, None, None
+        gs = _qparam_grad(gs, s, ctx.needs_input_grad[1])
+        gz = _qparam_grad(gz, z, learn_zp and ctx.needs_input_grad[2])
+        return gx, gs, gz, None, None, None, None, None
 
 
 class PerChannelObserveFQFn(torch.autograd.Function):
@@ -970,7 +969,6 @@ class PerChannelObserveFQFn(torch.autograd.Function):
                                    eps=eps, run_min=run_min, run_max=run_max, want_mask=True,
                                    want_row_stats=want_row_stats)
         ctx.save_for_backward(r["mask"], r["scale"])
-        ctx.rowlen = x.numel() // x.shape[0]
         rs = r["row_stats"] if want_row_stats else r["scale"].new_zeros(0)
         ctx.mark_non_differentiable(r["scale"], r["zp"], rs)
         return r["y"], r["scale"], r["zp"], rs
@@ -978,8 +976,7 @@ class PerChannelObserveFQFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, _gs, _gz, _gr):
         mask, scale = ctx.saved_tensors
-        gx = ste_backward(gy.contiguous(), mask, scale, ctx.rowlen)
-        return gx, None, None, None, None, None, None, None, None
+        return pc_ste_backward(gy, mask, scale), None, None, None, None, None, None, None, None
 
 
 # --------------------------------------------------------------------------- per-channel MSE
@@ -1007,20 +1004,11 @@ def per_channel_observe_mse(x: torch.Tensor, *, symmetric: bool, qmin: int, qmax
     dev = x.device
     C = x.shape[0] if x.dim() > 0 else 1
     rowlen = x.numel() // max(C, 1)
-    if run_min is None or run_max is None:   # fresh observer state 0/0 (minmax.py:28-29), one fill
-        state = torch.zeros(2, C, dtype=torch.float32, device=dev)
-        run_min = state[0] if run_min is None else run_min
-        run_max = state[1] if run_max is None else run_max
-    if run_min.numel() != C or run_max.numel() != C:
-        raise ValueError(f"running state has {run_min.numel()} channels, tensor has {C}")
-    y = torch.empty_like(x) if quantize else None
-    scale = torch.empty(C, dtype=torch.float64, device=dev)
-    zp = torch.empty(C, dtype=torch.float64, device=dev)
+    run_min, run_max, y, scale, zp, rstats = H.pc_observe_buffers(x, C, run_min, run_max, quantize, want_row_stats)
     clip = torch.empty(C, 2, dtype=torch.float64, device=dev)
     err = torch.empty(C, len(r), dtype=torch.float64, device=dev)
     pick = torch.empty(C, dtype=torch.int32, device=dev)
     mask = H.mask_buffer(C, rowlen, dev) if (want_mask and quantize) else None
-    rstats = torch.empty(C, 3, dtype=torch.float64, device=dev) if want_row_stats else None
     table = (H.c_d * len(r))(*r)
     rc = H.lib().vsiq_pc_observe_mse_f32(H.ptr(x), H.ptr(y), None, H.ptr(mask), _i64(C), _i64(rowlen), table, len(r),
                                          H.ptr(run_min), H.ptr(run_max), H.ptr(scale), H.ptr(zp), H.ptr(clip),
@@ -1041,7 +1029,6 @@ class PerChannelObserveMSEFn(torch.autograd.Function):
                                     run_min=run_min, run_max=run_max, ratios=ratios, want_mask=True,
                                     want_row_stats=want_row_stats)
         ctx.save_for_backward(r["mask"], r["scale"])
-        ctx.rowlen = x.numel() // x.shape[0]
         rs = r["row_stats"] if want_row_stats else r["scale"].new_zeros(0)
         ctx.mark_non_differentiable(r["scale"], r["zp"], rs, r["err"], r["pick"])
         return r["y"], r["scale"], r["zp"], rs, r["err"], r["pick"]
@@ -1049,8 +1036,7 @@ class PerChannelObserveMSEFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, _gs, _gz, _gr, _ge, _gp):
         mask, scale = ctx.saved_tensors
-        gx = ste_backward(gy.contiguous(), mask, scale, ctx.rowlen)
-        return gx, None, None, None, None, None, None, None, None, None
+        return pc_ste_backward(gy, mask, scale), None, None, None, None, None, None, None, None, None
 
 
 # --------------------------------------------------------------------------- export
@@ -1144,6 +1130,23 @@ def _pack_scalar_f64(v, dev):
     raise TypeError(f"unsupported qparam type {type(v).__name__}")
 
 
+def _row_qparams(t, scale, zero_point, axis, what):
+    """(rows, rowlen, nq, f64 scale [nq], f64 zp [nq] | None) of a pack or AdaRound call on t, on
+    t's device: axis None one row and scalar qparams, axis 0 one row and one (scale, zero
+    point) per out-channel (a number is every channel's)."""
+    if axis not in (None, 0):
+        raise ValueError(f"{what}: axis must be 0 or None, got {axis!r}")
+    rows, rowlen = _pack_view(t.shape, axis)
+    dev = t.device
+    if axis is None:
+        s = _pack_scalar_f64(scale, dev)
+        z = _pack_scalar_f64(zero_point, dev) if zero_point is not None else None
+        return rows, rowlen, 1, s, z
+    s = _per_channel_f64(scale, rows, dev, "scale")
+    z = _per_channel_f64(zero_point, rows, dev, "zero point") if zero_point is not None else None
+    return rows, rowlen, rows, s, z
+
+
 def quantize_pack(x: torch.Tensor, scale, zero_point, qmin: int, qmax: int, *, bits=None, axis=None,
                   zp_round: bool = False) -> PackedTensor:
     """Quantize x to the integer codes clamp(rint(x/s + zp), qmin, qmax) of the forward
@@ -1167,19 +1170,8 @@ def quantize_pack(x: torch.Tensor, scale, zero_point, qmin: int, qmax: int, *, b
         raise ValueError(f"packed bits must be one of {PACK_BITS}, got {bits}")
     if qmin > qmax or qmax - qmin + 1 > 2 ** bits:
         raise ValueError(f"the grid [{qmin}, {qmax}] does not fit {bits}-bit fields")
-    if axis not in (None, 0):
-        raise ValueError(f"quantize_pack: axis must be 0 or None, got {axis!r}")
-    rows, rowlen = _pack_view(x.shape, axis)
+    rows, rowlen, nq, s, z = _row_qparams(x, scale, zero_point, axis, "quantize_pack")
     dev = x.device
-    if axis == 0:
-        nq = rows
-        as_t = lambda v: v if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
-        s = _per_channel_f64(as_t(scale), rows, dev, "scale")
-        z = _per_channel_f64(as_t(zero_point), rows, dev, "zero point") if zero_point is not None else None
-    else:
-        nq = 1
-        s = _pack_scalar_f64(scale, dev)
-        z = _pack_scalar_f64(zero_point, dev) if zero_point is not None else None
     if dev.type == "cpu":
         data, qparams = _host.quantize_pack(x, s, z, nq, rows, rowlen, qmin, qmax, bits, zp_round)
         return PackedTensor(data, x.shape, bits, qmin, qmax, qparams, axis)
@@ -1212,7 +1204,7 @@ def unpack_dequant(p: PackedTensor, dtype=torch.float32, want_codes: bool = Fals
     if dev.type != "cuda":
         raise H.VsiqError(f"packed data is on {dev}: unpack_dequant runs on MI355X (HIP) or on CPU tensors")
     y = torch.empty(p.shape, dtype=dtype, device=dev)
-    codes = torch.empty(p.shape, dtype=torch.int8 if p.qmin < 0 else torch.uint8, device=dev) if want_codes else None
+    codes = H.codes_buffer(p.shape, p.qmin, dev) if want_codes else None
     rc = H.lib().vsiq_unpack_dequant(H.ptr(data), H.ptr(y), H.ptr(codes), _i64(rows), _i64(rowlen), H.ptr(qparams),
                                      _i64(qparams.shape[0]), p.qmin, p.bits, H._DT_CODES[dtype], H.stream_of(dev))
     H.check(rc, "vsiq_unpack_dequant")
@@ -1236,22 +1228,6 @@ def _ada_tensor(t, what, like=None):
     return t.detach().contiguous()
 
 
-def _ada_qparams(w, scale, zero_point, axis):
-    """(rows, rowlen, nq, f64 scale, f64 zp | None) of an AdaRound call, the pack entries' rules."""
-    if axis not in (None, 0):
-        raise ValueError(f"adaround: axis must be 0 or None, got {axis!r}")
-    rows, rowlen = _pack_view(w.shape, axis)
-    dev = w.device
-    if axis == 0:
-        as_t = lambda v: v if isinstance(v, torch.Tensor) else torch.tensor(float(v), dtype=torch.float64)  # noqa: E731
-        s = _per_channel_f64(as_t(scale), rows, dev, "scale")
-        z = _per_channel_f64(as_t(zero_point), rows, dev, "zero point") if zero_point is not None else None
-        return rows, rowlen, rows, s, z
-    s = _pack_scalar_f64(scale, dev)
-    z = _pack_scalar_f64(zero_point, dev) if zero_point is not None else None
-    return rows, rowlen, 1, s, z
-
-
 def adaround_forward(w, V, scale, zero_point, qmin: int, qmax: int, *, axis=None, hard: bool = False,
                      beta=None, zp_round: bool = False, want_y: bool = True):
     """AdaRound's forward (include/vsiq.h, "AdaRound"): y = (clamp(floor(w/s + z) + h(V)) - z) * s
@@ -1266,16 +1242,13 @@ def adaround_forward(w, V, scale, zero_point, qmin: int, qmax: int, *, axis=None
         raise ValueError("adaround_forward: nothing to compute (want_y=False and no beta)")
     if hard and beta is not None:
         raise ValueError("adaround_forward: the regulariser belongs to the soft forward (hard=True with beta)")
-    rows, rowlen, nq, s, z = _ada_qparams(w, scale, zero_point, axis)
+    rows, rowlen, nq, s, z = _row_qparams(w, scale, zero_point, axis, "adaround")
     dev = w.device
     y = torch.empty_like(w) if want_y else None
     reg = torch.empty((), dtype=torch.float64, device=dev) if beta is not None else None
     b = float(beta) if beta is not None else 1.0
     if dev.type == "cpu":
-        rc = H.lib().vsiq_host_adaround_fwd_f32(H.ptr(w), H.ptr(V), H.ptr(y), None, _i64(rows), _i64(rowlen),
-                                                H.ptr(s), H.ptr(z), _i64(nq), int(bool(zp_round)), int(qmin),
-                                                int(qmax), int(bool(hard)), b, H.ptr(reg))
-        H.check(rc, "vsiq_host_adaround_fwd_f32")
+        _host.adaround_forward(w, V, y, reg, rows, rowlen, s, z, nq, zp_round, qmin, qmax, hard, b)
         return y, reg
     ws = wsl = cnt = None
     if reg is not None:
@@ -1298,14 +1271,11 @@ def adaround_backward(g, w, V, scale, zero_point, qmin: int, qmax: int, *, axis=
     w = _ada_tensor(w, "w")
     V = _ada_tensor(V, "V", w)
     g = _ada_tensor(g, "grad_output", w)
-    rows, rowlen, nq, s, z = _ada_qparams(w, scale, zero_point, axis)
+    rows, rowlen, nq, s, z = _row_qparams(w, scale, zero_point, axis, "adaround")
     dev = w.device
     gv = torch.empty_like(V)
     if dev.type == "cpu":
-        rc = H.lib().vsiq_host_adaround_bwd_f32(H.ptr(g), H.ptr(w), H.ptr(V), H.ptr(gv), _i64(rows), _i64(rowlen),
-                                                H.ptr(s), H.ptr(z), _i64(nq), int(bool(zp_round)), int(qmin),
-                                                int(qmax), float(lam), float(beta))
-        H.check(rc, "vsiq_host_adaround_bwd_f32")
+        _host.adaround_backward(g, w, V, gv, rows, rowlen, s, z, nq, zp_round, qmin, qmax, lam, beta)
         return gv
     rc = H.lib().vsiq_adaround_bwd_f32(H.ptr(g), H.ptr(w), H.ptr(V), H.ptr(gv), _i64(rows), _i64(rowlen), H.ptr(s),
                                        H.ptr(z), _i64(nq), int(bool(zp_round)), int(qmin), int(qmax), float(lam),

@@ -9,6 +9,10 @@ or without AVX-512 (VSIQ_HOST_SIMD=0) and for any thread count, but a different 
 from the GPU's tree (equal to it within the f64 rounding of the sum).  This is not a
 fallback for CUDA tensors: a CUDA tensor never comes here, and a missing library raises
 like every other op.
+
+Only this module calls a vsiq_host_* entry point, and it decides nothing: fakequant.py
+sends a CPU tensor here (``is_host``), one plain function per op, and owns the autograd
+Functions of both sides.
 """
 from __future__ import annotations
 
@@ -18,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _hip as H
+from ._hip import qden
 
 
 def is_host(x) -> bool:
@@ -45,13 +50,20 @@ def _f32(x, what="x"):
     return x.contiguous()
 
 
+def _check_state(*states):
+    """The running state the host loops update in place: contiguous CPU float32, or None."""
+    for r in states:
+        if r is not None and (r.device.type != "cpu" or r.dtype != torch.float32 or not r.is_contiguous()):
+            raise ValueError("host observe: the running state must be a contiguous CPU float32 tensor")
+
+
 def fake_quant(x, scale, zero_point, qmin, qmax, *, zp_round=False, qp=None, want_mask=False, want_codes=False,
                discrete=False, act=None):
     """Host counterpart of fakequant.fake_quant: (y, mask uint8 | None, codes | None)."""
     x = _f32(x)
     y = torch.empty_like(x)
     mask = torch.empty(x.shape, dtype=torch.uint8) if want_mask else None
-    codes = torch.empty(x.shape, dtype=torch.int8 if qmin < 0 else torch.uint8) if want_codes else None
+    codes = H.codes_buffer(x.shape, qmin, "cpu") if want_codes else None
     if qp is not None:
         qp = qp.detach().to("cpu", torch.float64).contiguous()
         s = z = 0.0
@@ -63,83 +75,43 @@ def fake_quant(x, scale, zero_point, qmin, qmax, *, zp_round=False, qp=None, wan
     return y, mask, codes
 
 
-class FixedFn(torch.autograd.Function):
-    """Fixed-qparam fake quant with the reference's STE gradient, on the host."""
-
-    @staticmethod
-    def forward(ctx, x, scale, zero_point, qmin, qmax, qp, act=None):
-        y, mask, _ = fake_quant(x, scale, zero_point, qmin, qmax, qp=qp, want_mask=True, act=act)
-        ctx.code = H.act_code(act)
-        ctx.save_for_backward(mask, x.contiguous())
-        ctx.scale = float(qp[H.QP_SCALE]) if qp is not None else _num(scale)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        mask, x = ctx.saved_tensors
-        g = _f32(gy, "grad_output")
-        gx = torch.empty_like(g)
-        rc = H.lib().vsiq_host_ste_bwd_f32(H.ptr(g), H.ptr(mask), H.ptr(x), H.ptr(gx), _i64(g.numel()), ctx.code,
-                                           ctx.scale)
-        H.check(rc, "vsiq_host_ste_bwd_f32")
-        return gx, None, None, None, None, None, None
+def ste_backward(g, mask, scale, *, pre=None, act=None):
+    """Host counterpart of fakequant.ste_backward, per-tensor form (``mask``: fake_quant's
+    bytes): gx = (mask ? g*s : 0) / s, then the activation's backward at ``pre``."""
+    g = _f32(g, "grad_output")
+    code = H.act_code(act)
+    pre = _f32(pre, "pre-activation") if code != H.ACT_NONE else None
+    gx = torch.empty_like(g)
+    rc = H.lib().vsiq_host_ste_bwd_f32(H.ptr(g), H.ptr(mask), H.ptr(pre), H.ptr(gx), _i64(g.numel()), code,
+                                       _num(scale))
+    H.check(rc, "vsiq_host_ste_bwd_f32")
+    return gx
 
 
-class LearnFn(torch.autograd.Function):
-    """Learnable fake quant (uniform.py:47-56) on the host: forward as fake_quant with the
-    (rounded, clamped) zero point, backward grad_x + the f64 closed-form scale / zero-point
-    gradients times the ScaleGradient factor."""
-
-    @staticmethod
-    def forward(ctx, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None):
-        x = _f32(x)
-        y, _, _ = fake_quant(x, scale, zero_point, qmin, qmax, zp_round=learn_zp == 1, act=act)
-        ctx.save_for_backward(x)
-        ctx.scale, ctx.zp = scale, zero_point
-        ctx.args = (int(qmin), int(qmax), float(gscale), int(learn_zp), H.act_code(act))
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        qmin, qmax, gscale, learn_zp, code = ctx.args
-        s, z = ctx.scale, ctx.zp
-        g = _f32(gy, "grad_output")
-        gx = torch.empty_like(g)
-        grads = torch.empty(2, dtype=torch.float64)
-        rc = H.lib().vsiq_host_lsq_bwd_f32(H.ptr(g), H.ptr(x), H.ptr(gx), _i64(g.numel()), code, _num(s), _num(z),
-                                           int(learn_zp), qmin, qmax, gscale, H.ptr(grads))
-        H.check(rc, "vsiq_host_lsq_bwd_f32")
-        gs = gz = None
-        if isinstance(s, torch.Tensor) and ctx.needs_input_grad[1]:
-            gs = grads[0].to(device=s.device, dtype=s.dtype).reshape(s.shape)
-        if learn_zp and isinstance(z, torch.Tensor) and ctx.needs_input_grad[2]:
-            gz = grads[1].to(device=z.device, dtype=z.dtype).reshape(z.shape)
-        return gx, gs, gz, None, None, None, None, None
-
-
-def fake_quant_fixed(x, scale, zero_point, qmin, qmax, qp=None, act=None):
-    if x.requires_grad and torch.is_grad_enabled():
-        return FixedFn.apply(x, scale, zero_point, qmin, qmax, qp, act)
-    return fake_quant(x, scale, zero_point, qmin, qmax, qp=qp, act=act)[0]
-
-
-def fake_quant_learn(x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None):
-    return LearnFn.apply(x, scale, zero_point, qmin, qmax, gscale, learn_zp, act)
+def lsq_backward(g, x, scale, zero_point, qmin, qmax, gscale, learn_zp, act=None):
+    """Host counterpart of fakequant.lsq_backward (uniform.py:47-56): grad_x and f64[2], the
+    closed-form scale / zero-point gradients times the ScaleGradient factor."""
+    g = _f32(g, "grad_output")
+    x = _f32(x)
+    gx = torch.empty_like(g)
+    grads = torch.empty(2, dtype=torch.float64)
+    rc = H.lib().vsiq_host_lsq_bwd_f32(H.ptr(g), H.ptr(x), H.ptr(gx), _i64(g.numel()), H.act_code(act), _num(scale),
+                                       _num(zero_point), int(learn_zp), int(qmin), int(qmax), float(gscale),
+                                       H.ptr(grads))
+    H.check(rc, "vsiq_host_lsq_bwd_f32")
+    return gx, grads
 
 
 def observe_tensor(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, want_qp=True, want_stats=True,
                    act=None):
     """Host counterpart of fakequant.observe_tensor: one pass -> running update (fp32[2]
     CPU state) -> f64 qparams record, stats record."""
-    from .fakequant import qden
     x = _f32(x)
     if x.numel() == 0:
-        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+        raise H.empty_error()
     qp = torch.empty(H.QP_LEN, dtype=torch.float64) if want_qp else None
     st = torch.empty(H.ST_LEN, dtype=torch.float64) if want_stats else None
-    if run_minmax is not None and (run_minmax.device.type != "cpu" or run_minmax.dtype != torch.float32):
-        raise ValueError("host observe: the running state must be a CPU float32 tensor")
+    _check_state(run_minmax)
     rc = H.lib().vsiq_host_observe_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), H.ptr(st), H.ptr(run_minmax),
                                        H.ptr(qp), int(bool(symmetric)), qden(symmetric, num_bits, eps), float(eps))
     H.check(rc, "vsiq_host_observe_f32")
@@ -149,12 +121,10 @@ def observe_tensor(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, want_
 def observe_percentile(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, tail, bins=2048, act=None):
     """Host counterpart of fakequant.observe_percentile: the host observer pass for the
     stats record, then the host histogram loop -> (qp, stats, clip f64[2])."""
-    from .fakequant import qden
     _, st = observe_tensor(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=None, want_qp=False,
                            act=act)
     x = _f32(x)
-    if run_minmax is not None and (run_minmax.device.type != "cpu" or run_minmax.dtype != torch.float32):
-        raise ValueError("host observe: the running state must be a CPU float32 tensor")
+    _check_state(run_minmax)
     qp = torch.empty(H.QP_LEN, dtype=torch.float64)
     clip = torch.empty(2, dtype=torch.float64)
     hist = torch.zeros(int(bins), dtype=torch.int64)
@@ -170,12 +140,10 @@ def observe_mse(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, ratios, 
     """Host counterpart of fakequant.observe_mse (which has validated ``ratios`` and the
     grid): the host observer pass for the stats record, then the host search loop ->
     (qp, stats, clip f64[2], err f64[len(ratios)], pick int32[1])."""
-    from .fakequant import qden
     _, st = observe_tensor(x, symmetric=symmetric, num_bits=num_bits, eps=eps, run_minmax=None, want_qp=False,
                            act=act)
     x = _f32(x)
-    if run_minmax is not None and (run_minmax.device.type != "cpu" or run_minmax.dtype != torch.float32):
-        raise ValueError("host observe: the running state must be a CPU float32 tensor")
+    _check_state(run_minmax)
     qp = torch.empty(H.QP_LEN, dtype=torch.float64)
     clip = torch.empty(2, dtype=torch.float64)
     err = torch.empty(len(ratios), dtype=torch.float64)
@@ -189,11 +157,20 @@ def observe_mse(x, *, symmetric, num_bits=8, eps=1e-8, run_minmax=None, ratios, 
     return qp, st, clip, err, pick
 
 
+def torch_mean(x, act, vec, threads):
+    """Host counterpart of fakequant.torch_mean (which has resolved the layout): fp32[4]."""
+    x = x.contiguous()
+    out = torch.empty(4, dtype=torch.float32)
+    rc = H.lib().vsiq_host_torch_mean_f32(H.ptr(x), _i64(x.numel()), H.act_code(act), vec, threads, H.ptr(out))
+    H.check(rc, "vsiq_host_torch_mean_f32")
+    return out
+
+
 # --------------------------------------------------------------------------- per-channel
 def _rows(x):
     C = x.shape[0] if x.dim() > 0 else 1
     if C == 0 or x.numel() == 0:
-        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+        raise H.empty_error()
     return C, x.numel() // C
 
 
@@ -208,7 +185,7 @@ def _pc_view(x, axis):
         raise ValueError(f"per-channel axis must be 0 or 1 of a tensor with more dims, got {axis}")
     C, rows = x.shape[1], x.shape[0] * x.shape[1]
     if rows == 0 or x.numel() == 0:
-        raise RuntimeError("min(): Expected reduction dim to be specified for input.numel() == 0.")
+        raise H.empty_error()
     return rows, x.numel() // rows, C
 
 
@@ -227,21 +204,11 @@ def pc_observe_fq(x, *, symmetric, qmin, qmax, obs_bits=8, eps=1e-8, run_min=Non
     """Host counterpart of fakequant.per_channel_observe_fq (K3): each out-channel row W[c]
     observed (running state per row) and fake-quantized with its own f64 qparams, the
     per-tensor host code on each row.  Same dict as the device function."""
-    from .fakequant import qden
     x = _f32(x)
     C, rowlen = _rows(x)
-    if run_min is None or run_max is None:
-        state = torch.zeros(2, C, dtype=torch.float32)
-        run_min = state[0] if run_min is None else run_min
-        run_max = state[1] if run_max is None else run_max
-    for r in (run_min, run_max):
-        if r.numel() != C or r.device.type != "cpu" or r.dtype != torch.float32 or not r.is_contiguous():
-            raise ValueError(f"host per-channel observe: running state must be contiguous CPU float32 [{C}]")
-    y = torch.empty_like(x) if quantize else None
+    run_min, run_max, y, scale, zp, rstats = H.pc_observe_buffers(x, C, run_min, run_max, quantize, want_row_stats)
+    _check_state(run_min, run_max)
     mask = torch.empty(x.shape, dtype=torch.uint8) if (want_mask and quantize) else None
-    scale = torch.empty(C, dtype=torch.float64)
-    zp = torch.empty(C, dtype=torch.float64)
-    rstats = torch.empty(C, 3, dtype=torch.float64) if want_row_stats else None
     rc = H.lib().vsiq_host_pc_observe_fq_f32(H.ptr(x), H.ptr(y), H.ptr(mask), _i64(C), _i64(rowlen), H.ptr(run_min),
                                              H.ptr(run_max), H.ptr(scale), H.ptr(zp), H.ptr(rstats),
                                              int(bool(symmetric)), qden(symmetric, obs_bits, eps), float(eps),
@@ -256,24 +223,14 @@ def pc_observe_mse(x, *, symmetric, qmin, qmax, num_bits=8, eps=1e-8, run_min=No
     """Host counterpart of fakequant.per_channel_observe_mse (which has validated ``ratios``
     and the grid): the host MSE loop on each row W[c] with its own running state, then the
     host per-channel fake quant with the qparams returned.  Same dict as the device function."""
-    from .fakequant import qden
     x = _f32(x)
     C, rowlen = _rows(x)
-    if run_min is None or run_max is None:
-        state = torch.zeros(2, C, dtype=torch.float32)
-        run_min = state[0] if run_min is None else run_min
-        run_max = state[1] if run_max is None else run_max
-    for r in (run_min, run_max):
-        if r.numel() != C or r.device.type != "cpu" or r.dtype != torch.float32 or not r.is_contiguous():
-            raise ValueError(f"host per-channel observe: running state must be contiguous CPU float32 [{C}]")
-    y = torch.empty_like(x) if quantize else None
+    run_min, run_max, y, scale, zp, rstats = H.pc_observe_buffers(x, C, run_min, run_max, quantize, want_row_stats)
+    _check_state(run_min, run_max)
     mask = torch.empty(x.shape, dtype=torch.uint8) if (want_mask and quantize) else None
-    scale = torch.empty(C, dtype=torch.float64)
-    zp = torch.empty(C, dtype=torch.float64)
     clip = torch.empty(C, 2, dtype=torch.float64)
     err = torch.empty(C, len(ratios), dtype=torch.float64)
     pick = torch.empty(C, dtype=torch.int32)
-    rstats = torch.empty(C, 3, dtype=torch.float64) if want_row_stats else None
     table = (H.c_d * len(ratios))(*ratios)
     rc = H.lib().vsiq_host_pc_observe_mse_f32(H.ptr(x), H.ptr(y), H.ptr(mask), _i64(C), _i64(rowlen), table,
                                               len(ratios), H.ptr(run_min), H.ptr(run_max), H.ptr(scale), H.ptr(zp),
@@ -301,6 +258,7 @@ def pc_fake_quant(x, scale, zp, qmin, qmax, *, zp_round=False, want_mask=False, 
 
 
 def pc_ste_backward(g, mask, scale, axis=0):
+    """Host counterpart of fakequant.pc_ste_backward (``mask``: pc_fake_quant's bytes)."""
     g = _f32(g, "grad_output")
     rows, rowlen, C = _pc_view(g, axis)
     s = _row_f64(scale, C, "scale")
@@ -311,112 +269,24 @@ def pc_ste_backward(g, mask, scale, axis=0):
     return gx
 
 
-class PcFixedFn(torch.autograd.Function):
-    """Per-channel fake quant with given [C] qparams and the STE backward, on the host
-    (``axis`` 0 or 1)."""
-
-    @staticmethod
-    def forward(ctx, x, scale, zp, qmin, qmax, axis=0):
-        y, mask = pc_fake_quant(x, scale, zp, qmin, qmax, want_mask=True, axis=axis)
-        ctx.save_for_backward(mask, _row_f64(scale, _pc_view(x, axis)[2], "scale"))
-        ctx.axis = axis
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        mask, s = ctx.saved_tensors
-        return pc_ste_backward(gy, mask, s, ctx.axis), None, None, None, None, None
-
-
-class PcObserveFQFn(torch.autograd.Function):
-    """Per-channel observe + fake quant with the STE backward, on the host."""
-
-    @staticmethod
-    def forward(ctx, x, symmetric, qmin, qmax, obs_bits, eps, run_min, run_max, want_row_stats):
-        r = pc_observe_fq(x, symmetric=symmetric, qmin=qmin, qmax=qmax, obs_bits=obs_bits, eps=eps,
-                          run_min=run_min, run_max=run_max, want_mask=True, want_row_stats=want_row_stats)
-        ctx.save_for_backward(r["mask"], r["scale"])
-        rs = r["row_stats"] if want_row_stats else r["scale"].new_zeros(0)
-        ctx.mark_non_differentiable(r["scale"], r["zp"], rs)
-        return r["y"], r["scale"], r["zp"], rs
-
-    @staticmethod
-    def backward(ctx, gy, _gs, _gz, _gr):
-        mask, scale = ctx.saved_tensors
-        return pc_ste_backward(gy, mask, scale), None, None, None, None, None, None, None, None
-
-
-class PcObserveMSEFn(torch.autograd.Function):
-    """pc_observe_mse with the STE backward, on the host: (y, scale, zp, row_stats, err, pick)."""
-
-    @staticmethod
-    def forward(ctx, x, symmetric, qmin, qmax, num_bits, eps, run_min, run_max, ratios, want_row_stats):
-        r = pc_observe_mse(x, symmetric=symmetric, qmin=qmin, qmax=qmax, num_bits=num_bits, eps=eps,
-                           run_min=run_min, run_max=run_max, ratios=ratios, want_mask=True,
-                           want_row_stats=want_row_stats)
-        ctx.save_for_backward(r["mask"], r["scale"])
-        rs = r["row_stats"] if want_row_stats else r["scale"].new_zeros(0)
-        ctx.mark_non_differentiable(r["scale"], r["zp"], rs, r["err"], r["pick"])
-        return r["y"], r["scale"], r["zp"], rs, r["err"], r["pick"]
-
-    @staticmethod
-    def backward(ctx, gy, _gs, _gz, _gr, _ge, _gp):
-        mask, scale = ctx.saved_tensors
-        return pc_ste_backward(gy, mask, scale), None, None, None, None, None, None, None, None, None
-
-
-class PcLearnFn(torch.autograd.Function):
-    """Learnable per-channel fake quant on the host (``axis`` 0: [C, ...] weights, 1:
+def pc_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, axis=0):
+    """Host counterpart of fakequant.pc_lsq_backward (``axis`` 0: [C, ...] weights, 1:
     [N, C, ...] activations -- LSQFakeQuantize): each row the per-tensor learnable host
-    path with its channel's scale / zero point; [C] gradients (f64 sums over each channel's
-    rows) times gscale."""
-
-    @staticmethod
-    def forward(ctx, x, scale, zero_point, qmin, qmax, gscale, learn_zp, axis=0):
-        x = _f32(x)
-        y, _ = pc_fake_quant(x, scale, zero_point, qmin, qmax, zp_round=learn_zp, axis=axis)
-        ctx.save_for_backward(x)
-        ctx.scale, ctx.zp = scale, zero_point
-        ctx.args = (int(qmin), int(qmax), float(gscale), int(bool(learn_zp)), axis)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        (x,) = ctx.saved_tensors
-        qmin, qmax, gscale, learn_zp, axis = ctx.args
-        s, z = ctx.scale, ctx.zp
-        g = _f32(gy, "grad_output")
-        rows, rowlen, C = _pc_view(x, axis)
-        sr = _row_f64(s, C, "scale")
-        zr = _row_f64(z, C, "zero point") if z is not None else None
-        gx = torch.empty_like(g)
-        gs = torch.empty(C, dtype=torch.float64)
-        gz = torch.empty(C, dtype=torch.float64)
-        rc = H.lib().vsiq_host_pcm_lsq_bwd_f32(H.ptr(g), H.ptr(x), H.ptr(gx), _i64(rows), _i64(rowlen), _i64(C),
-                                               H.ptr(sr), H.ptr(zr), learn_zp, qmin, qmax, gscale, H.ptr(gs),
-                                               H.ptr(gz))
-        H.check(rc, "vsiq_host_pcm_lsq_bwd_f32")
-        out_s = out_z = None
-        if isinstance(s, torch.Tensor) and ctx.needs_input_grad[1]:
-            out_s = gs.to(device=s.device, dtype=s.dtype).reshape(s.shape)
-        if learn_zp and isinstance(z, torch.Tensor) and ctx.needs_input_grad[2]:
-            out_z = gz.to(device=z.device, dtype=z.dtype).reshape(z.shape)
-        return gx, out_s, out_z, None, None, None, None, None
-
-
-def threads() -> int:
-    """Host threads the CPU path uses (VSIQ_HOST_THREADS, else the CPUs this process may use)."""
-    return int(H.lib().vsiq_host_threads())
-
-
-def simd() -> bool:
-    """True when the host loops run their AVX-512 form (csrc/host_simd.cpp)."""
-    return bool(H.lib().vsiq_host_simd())
-
-
-__all__ = ["is_host", "fake_quant", "fake_quant_fixed", "fake_quant_learn", "observe_tensor", "observe_percentile",
-           "observe_mse", "pc_observe_fq", "pc_observe_mse",
-           "pc_fake_quant", "quantize_pack", "unpack_dequant", "threads", "simd"]
+    path with its channel's scale / zero point; (grad_x, grad_scale f64 [C], grad_zp f64 [C]),
+    the f64 sums over each channel's rows times gscale."""
+    g = _f32(g, "grad_output")
+    x = _f32(x)
+    rows, rowlen, C = _pc_view(x, axis)
+    s = _row_f64(scale, C, "scale")
+    z = _row_f64(zp, C, "zero point") if zp is not None else None
+    gx = torch.empty_like(g)
+    gs = torch.empty(C, dtype=torch.float64)
+    gz = torch.empty(C, dtype=torch.float64)
+    rc = H.lib().vsiq_host_pcm_lsq_bwd_f32(H.ptr(g), H.ptr(x), H.ptr(gx), _i64(rows), _i64(rowlen), _i64(C),
+                                           H.ptr(s), H.ptr(z), int(bool(learn_zp)), int(qmin), int(qmax),
+                                           float(gscale), H.ptr(gs), H.ptr(gz))
+    H.check(rc, "vsiq_host_pcm_lsq_bwd_f32")
+    return gx, gs, gz
 
 
 # --------------------------------------------------------------------------- export
@@ -436,8 +306,42 @@ def quantize_pack(x, scale, zp, nq, rows, rowlen, qmin, qmax, bits, zp_round):
 def unpack_dequant(data, qparams, shape, rows, rowlen, qmin, bits, want_codes):
     """Host counterpart of fakequant.unpack_dequant: (y fp32, codes | None)."""
     y = torch.empty(shape, dtype=torch.float32)
-    codes = torch.empty(shape, dtype=torch.int8 if qmin < 0 else torch.uint8) if want_codes else None
+    codes = H.codes_buffer(shape, qmin, "cpu") if want_codes else None
     rc = H.lib().vsiq_host_unpack_dequant_f32(H.ptr(data), H.ptr(y), H.ptr(codes), _i64(rows), _i64(rowlen),
                                               H.ptr(qparams), _i64(qparams.shape[0]), int(qmin), int(bits))
     H.check(rc, "vsiq_host_unpack_dequant_f32")
     return y, codes
+
+
+# --------------------------------------------------------------------------- AdaRound
+def adaround_forward(w, V, y, reg, rows, rowlen, s, z, nq, zp_round, qmin, qmax, hard, beta):
+    """Host leg of fakequant.adaround_forward (which has checked the arguments and made the
+    outputs): writes y (or None) and the regulariser reg (or None)."""
+    rc = H.lib().vsiq_host_adaround_fwd_f32(H.ptr(w), H.ptr(V), H.ptr(y), None, _i64(rows), _i64(rowlen), H.ptr(s),
+                                            H.ptr(z), _i64(nq), int(bool(zp_round)), int(qmin), int(qmax),
+                                            int(bool(hard)), beta, H.ptr(reg))
+    H.check(rc, "vsiq_host_adaround_fwd_f32")
+
+
+def adaround_backward(g, w, V, gv, rows, rowlen, s, z, nq, zp_round, qmin, qmax, lam, beta):
+    """Host leg of fakequant.adaround_backward: writes grad_V into gv."""
+    rc = H.lib().vsiq_host_adaround_bwd_f32(H.ptr(g), H.ptr(w), H.ptr(V), H.ptr(gv), _i64(rows), _i64(rowlen),
+                                            H.ptr(s), H.ptr(z), _i64(nq), int(bool(zp_round)), int(qmin), int(qmax),
+                                            float(lam), float(beta))
+    H.check(rc, "vsiq_host_adaround_bwd_f32")
+
+
+def threads() -> int:
+    """Host threads the CPU path uses (VSIQ_HOST_THREADS, else the CPUs this process may use)."""
+    return int(H.lib().vsiq_host_threads())
+
+
+def simd() -> bool:
+    """True when the host loops run their AVX-512 form (csrc/host_simd.cpp)."""
+    return bool(H.lib().vsiq_host_simd())
+
+
+__all__ = ["is_host", "fake_quant", "ste_backward", "lsq_backward", "observe_tensor", "observe_percentile",
+           "observe_mse", "torch_mean", "pc_observe_fq", "pc_observe_mse", "pc_fake_quant", "pc_ste_backward",
+           "pc_lsq_backward", "quantize_pack", "unpack_dequant", "adaround_forward", "adaround_backward", "threads",
+           "simd"]

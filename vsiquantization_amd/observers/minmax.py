@@ -130,7 +130,7 @@ class MinMaxObserver(BaseObserver):
         ``act``: observe act(x) (fused ReLU/SiLU, K5) without materializing it."""
         if self._defer_owner is not None:
             self._fold_owner()
-        if host.is_host(x):   # CPU tensor: the native host pass (host.py), CPU fp32[2] state
+        if host.is_host(x):   # CPU tensor: a CPU fp32[2] state and no observer stream to join
             dev = x.device
         else:
             dev = H.require_device_float(x)[0].device   # fp32, or bf16 / fp16 (typed K2)

@@ -65,11 +65,11 @@ class PerChannelMinMaxObserver(BaseObserver):
 
     # ------------------------------------------------------------------ protocol
     def observe(self, x, want_row_stats=False):
+        # checked before _state, which drops the running min / max when the device changes
         x = x if _host.is_host(x) else H.require_device_f32(x)
         mn, mx = self._state(x)
-        fn = _host.pc_observe_fq if _host.is_host(x) else per_channel_observe_fq
-        r = fn(x, symmetric=self.symmetric, qmin=0, qmax=0, obs_bits=self.num_bits, eps=self.eps,
-               run_min=mn, run_max=mx, quantize=False, want_row_stats=want_row_stats)
+        r = per_channel_observe_fq(x, symmetric=self.symmetric, qmin=0, qmax=0, obs_bits=self.num_bits, eps=self.eps,
+                                   run_min=mn, run_max=mx, quantize=False, want_row_stats=want_row_stats)
         self.scale, self.zero_point = r["scale"], r["zp"]
         return r["row_stats"]
 
@@ -110,21 +110,10 @@ class PerChannelMinMaxObserver(BaseObserver):
             if r is not None:
                 y, self.scale, self.zero_point = r
                 return y, None
-        if _host.is_host(x):
-            mn, mx = self._state(x)
-            args = (self.symmetric, quantizer.qmin, quantizer.qmax, self.num_bits, self.eps, mn, mx)
-            if x.requires_grad and torch.is_grad_enabled():
-                y, s, z, rs = _host.PcObserveFQFn.apply(x, *args, want_row_stats)
-                rs = rs if want_row_stats else None
-            else:
-                r = _host.pc_observe_fq(x, symmetric=args[0], qmin=args[1], qmax=args[2], obs_bits=args[3],
-                                        eps=args[4], run_min=mn, run_max=mx, want_row_stats=want_row_stats)
-                y, s, z, rs = r["y"], r["scale"], r["zp"], r["row_stats"]
-            self.scale, self.zero_point = s, z
-            return y, rs
-        x = H.require_device_f32(x)
+        host = _host.is_host(x)   # a CPU tensor never takes the C++ op; checked before _state, as in observe
+        x = x if host else H.require_device_f32(x)
         mn, mx = self._state(x)
-        if H.torch_ext_enabled():   # C++ op (_vsiq_torch.so): an autograd node when x needs one
+        if H.torch_ext_enabled() and not host:   # C++ op (_vsiq_torch.so): an autograd node when x needs one
             y, s, z, rs = H.torch_ext().pc_observe_fq(x, mn, mx, bool(self.symmetric), int(quantizer.qmin),
                                                       int(quantizer.qmax), qden(self.symmetric, self.num_bits, self.eps),
                                                       float(self.eps), bool(want_row_stats))

@@ -53,6 +53,7 @@ class PerChannelMSEObserver(PerChannelMinMaxObserver):
         return 0, 2 ** self.num_bits - 1
 
     def _check(self, x):
+        # before _state, which drops the running min / max when the device changes
         return x if _host.is_host(x) else H.require_device_f32(x)
 
     # ------------------------------------------------------------------ protocol
@@ -75,9 +76,9 @@ class PerChannelMSEObserver(PerChannelMinMaxObserver):
         x = self._check(x)
         mn, mx = self._state(x)
         if x.requires_grad and torch.is_grad_enabled():
-            fn = _host.PcObserveMSEFn if _host.is_host(x) else PerChannelObserveMSEFn
-            y, s, z, rs, err, pick = fn.apply(x, self.symmetric, quantizer.qmin, quantizer.qmax, self.num_bits,
-                                              self.eps, mn, mx, self.ratios, want_row_stats)
+            y, s, z, rs, err, pick = PerChannelObserveMSEFn.apply(x, self.symmetric, quantizer.qmin, quantizer.qmax,
+                                                                  self.num_bits, self.eps, mn, mx, self.ratios,
+                                                                  want_row_stats)
             rs = rs if want_row_stats else None
         else:
             r = per_channel_observe_mse(x, symmetric=self.symmetric, qmin=quantizer.qmin, qmax=quantizer.qmax,

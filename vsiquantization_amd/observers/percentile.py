@@ -38,7 +38,7 @@ class PercentileObserver(MinMaxObserver):
     def observe_device(self, x, want_stats=True, want_qp=True, act=None):
         """K2 + the histogram pass: update the running state from the clipped range, return
         (qp f64[4], stats f64[10]) on x.device; the stats are the unclipped tensor's."""
-        if host.is_host(x):
+        if host.is_host(x):   # CPU tensor: a CPU fp32[2] state and no observer stream to join
             dev = x.device
         else:
             dev = H.require_device_f32(x).device

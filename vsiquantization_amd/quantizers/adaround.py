@@ -14,7 +14,7 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..fakequant import AdaRoundFn, _ada_qparams, _ada_tensor, adaround_forward
+from ..fakequant import AdaRoundFn, _ada_tensor, _row_qparams, adaround_forward
 
 ZETA, GAMMA = 1.1, -0.1
 
@@ -40,7 +40,7 @@ class AdaRoundWeight(nn.Module):
         w = _ada_tensor(w, "w")
         per_channel = any(isinstance(v, torch.Tensor) and v.dim() == 1 and v.numel() > 1 for v in (s, z))
         axis = 0 if per_channel else None
-        _, _, _, s64, z64 = _ada_qparams(w, s, z, axis)
+        _, _, _, s64, z64 = _row_qparams(w, s, z, axis, "adaround")
         self._q = (s64, z64, int(lo), int(hi), axis)
         # plain torch, once: frac = t - floor(t) of the forward's own t = RN(RN(w/s) + z).
         # Each fp32 operation is done in f64 and rounded to fp32 (53 >= 2 * 24 + 2 bits: the

@@ -17,8 +17,7 @@ The fake quant itself runs in the HIP kernels: per-tensor K1 forward + K4 backwa
 per-channel (the reference broadcasts the parameters along dim 1,
 lsq_module.py:141-143) K3-fixed forward + K6 backward -- bit-exact fp32 forward and
 grad_x, f64-summed parameter gradients.  CPU tensors take the native host loops
-(host.py: per tensor vsiq_host_*, per channel vsiq_host_pcm_* over the [N, C, ...]
-rows), with the same bits.  The observer (torch.ao, third-party) and the experimental
+(host.py: per tensor, and per channel over the [N, C, ...] rows), with the same bits.  The observer (torch.ao, third-party) and the experimental
 adaptive rounding (``flag_adaptive``, theta/gamma; the reference never sets it,
 lsq_module.py:93) keep the reference's torch implementation.
 """
@@ -27,7 +26,6 @@ from __future__ import annotations
 import torch
 from torch.ao.quantization import FakeQuantize, MovingAverageMinMaxObserver
 
-from .. import host as _host
 from ..fakequant import PerChannelFQFn, PerChannelLearnFn, fake_quant_fixed, fake_quant_learn
 
 
@@ -126,10 +124,6 @@ class LSQFakeQuantize(FakeQuantize):
                 return self._fq_reference(X, scale, zero_point, qmin, qmax)
             if self.is_per_channel:
                 self._check_channels(X, scale)
-                if X.device.type == "cpu":   # the host loops, [N, C, ...] rows
-                    if X.requires_grad and torch.is_grad_enabled():
-                        return _host.PcFixedFn.apply(X, scale, zero_point, qmin, qmax, 1)
-                    return _host.pc_fake_quant(X, scale, zero_point, qmin, qmax, axis=1)[0]
                 return PerChannelFQFn.apply(X, scale, zero_point, qmin, qmax, 1)
             return fake_quant_fixed(X, scale, zero_point, qmin, qmax)
         return X
@@ -139,13 +133,13 @@ class LSQFakeQuantize(FakeQuantize):
         if X.dim() < 2 or (param.numel() != X.shape[1] and param.numel() != 1):
             raise RuntimeError(f"The size of tensor a ({X.shape[1] if X.dim() > 1 else 1}) must match the "
                                f"size of tensor b ({param.numel()}) at non-singleton dimension 1")
+        if X.device.type == "cpu" and X.dtype != torch.float32:   # as this path always said it (not "not on the GPU")
+            raise TypeError(f"x: only float32 is supported by the fake-quant path, got {X.dtype}")
 
     def _learnable(self, X, grad_scale, qmin, qmax):
         s, z = self.scale_param, self.zero_point_param_float
         if self.is_per_channel:
             self._check_channels(X, s)
-            if X.device.type == "cpu":   # the host loops, [N, C, ...] rows
-                return _host.PcLearnFn.apply(X, s, z, qmin, qmax, float(grad_scale), True, 1)
             return PerChannelLearnFn.apply(X, s, z, qmin, qmax, float(grad_scale), True, 1)
         return fake_quant_learn(X, s, z, qmin, qmax, float(grad_scale), True)
 
