@@ -840,6 +840,53 @@ int vsiq_host_adaround_bwd_f32(const float *g, const float *w, const float *v, f
                                int qmin, int qmax, double lam, double beta);
 
 /*
+ * MX block-scaled fake quantization (OCP Microscaling Formats v1.0; added without an ABI
+ * bump).  32 consecutive elements along one axis share one power-of-two E8M0 scale X = 2^E;
+ * each element is a 4-, 6- or 8-bit float.  No observer, no qparams, no workspace.
+ *
+ *   fmt               bits  emax  max normal  min normal  mantissa bits  overflow value
+ *   VSIQ_MX_FP4_E2M1   4     2     6           1           1              8
+ *   VSIQ_MX_FP6_E2M3   6     2     7.5         1           3              8
+ *   VSIQ_MX_FP6_E3M2   6     4     28          0.25        2              32
+ *   VSIQ_MX_FP8_E4M3   8     8     448         2^-6        3              480
+ *   VSIQ_MX_FP8_E5M2   8     15    57344       2^-14       2              65536
+ *
+ * Per block with finite values, amax = max |v_i| (the last block of a row may be shorter):
+ *   E = clamp(floor(log2(amax)) - emax, -127, 127), from amax's exponent field (an fp32
+ *       denormal or zero amax gives -127); scale byte E + 127
+ *   a_i = |v_i| * 2^-E (exact);  q_i = the value nearest a_i on the format's grid (its
+ *       subnormals and zero included) extended by the overflow value, ties to the even
+ *       mantissa; the overflow value then becomes max normal
+ *   y_i = sign(v_i) * q_i * 2^E (exact in fp32).  Signed zeros keep their sign.
+ *   mask bit = 1 iff rounding did not pick the overflow value (FP4: a < 7 rounds to 6, in
+ *       range; a >= 7 is masked)
+ *   code byte = sign in the field's top bit (bit `bits` - 1), then q_i's exponent and
+ *       mantissa fields in the OCP layout; one byte per element
+ * An all-zero block: scale byte 0, y = v, mask 1, codes the sign only.  A block holding a
+ * NaN or an Inf: scale byte 255 and every y of the block NaN (0x7fc00000), mask 0, codes 0.
+ *
+ * Host entry points only (fp32 host pointers; there is no device kernel for this yet, a CUDA
+ * tensor is refused by the Python layer).  Row form (vsiq_host_mx_fq_fwd_f32): x [rows,
+ * rowlen] contiguous, blocks along each row; scales [rows][ceil(rowlen / 32)] =
+ * vsiq_mx_blocks(rows, rowlen) bytes.  Column form (vsiq_host_mx_fq_fwd_cols_f32): x [outer,
+ * channels, inner] contiguous, blocks of 32 along `channels` (an NCHW activation's channel
+ * axis); scales [outer][ceil(channels / 32)][inner].  codes, scales and mask are nullable;
+ * mask is one byte per element (vsiq_host_ste_bwd_f32's layout, so that call with scale 1 is
+ * the backward).  VSIQ_E_ARG: an unknown fmt, a size <= 0, x or y NULL (codes / scales /
+ * mask without y included).
+ */
+#define VSIQ_MX_FP4_E2M1 0
+#define VSIQ_MX_FP6_E2M3 1
+#define VSIQ_MX_FP6_E3M2 2
+#define VSIQ_MX_FP8_E4M3 3
+#define VSIQ_MX_FP8_E5M2 4
+int64_t vsiq_mx_blocks(int64_t rows, int64_t rowlen);
+int vsiq_host_mx_fq_fwd_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales, uint8_t *mask, int64_t rows,
+                            int64_t rowlen, int fmt);
+int vsiq_host_mx_fq_fwd_cols_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales, uint8_t *mask,
+                                 int64_t outer, int64_t channels, int64_t inner, int fmt);
+
+/*
  * BatchNorm folding (modules/fused.py:100-108, :294-300), fp32, reference order:
  *   f = gamma / sqrt(running_var + eps);  w_out[r,:] = w[r,:] * f[r]
  *   b_out[r] = beta[r] + (b[r] - running_mean[r]) * f[r]      (b NULL: 0; b_out nullable)

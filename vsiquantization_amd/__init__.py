@@ -9,6 +9,7 @@ Importing the package registers the quantizer/observer classes by name in
   PerChannelUniformQuantizer, PerChannelMinMaxObserver  (per-channel, axis 0)
   PercentileObserver, MSEObserver                   (calibrators that clip the min / max range)
   PerChannelMSEObserver                             (MSEObserver's search on every out-channel row)
+  MXQuantizer                                       (OCP MX block scaling: MXFP4 / MXFP6 / MXFP8)
 
 plus ``LSQFakeQuantize`` (quantizers/lsq_module.py, the torch.ao-based LSQ module).
 All fake-quant arithmetic runs in the HIP kernels of ``csrc/`` through the C ABI of
@@ -39,6 +40,8 @@ from .utils.export import export_packed_state, packed_state_weights  # noqa: F40
 from .fakequant import adaround_backward, adaround_forward  # noqa: F401
 from .quantizers.adaround import AdaRoundWeight  # noqa: F401
 from .utils.adaround import adaround_layer, adaround_model  # noqa: F401
+from .fakequant import mx_dequant, mx_fake_quant  # noqa: F401
+from .quantizers.mx import MXQuantizer  # noqa: F401
 from .utils.quantize_manager import (disable_model_launches, enable_model_launches,  # noqa: F401
                                      model_launches_enabled)
 

@@ -47,6 +47,10 @@ TUNE_K2O_FORM, TUNE_K2O_GROUPS, TUNE_K2O_BLOCK = 14, 15, 17
 REMOVED_TUNE_KEYS = (1, 5, 8, 16)   # ABI 10: K3 rows / workgroup size, K2 grid, K2 cached-load threshold
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2   # VSIQ_DT_*: the element type of the typed (_t) entry points
+# VSIQ_MX_*: element formats of the MX block-scaled fake quant -> (fmt code, bits, exponent
+# bits, mantissa bits, exponent bias)
+MX_FORMATS = {"fp4_e2m1": (0, 4, 2, 1, 1), "fp6_e2m3": (1, 6, 2, 3, 1), "fp6_e3m2": (2, 6, 3, 2, 3),
+              "fp8_e4m3": (3, 8, 4, 3, 7), "fp8_e5m2": (4, 8, 5, 2, 15)}
 ACT_CODES = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "silu": ACT_SILU}
 
 # SiLU bit for bit as torch's CPU kernel on this host (include/vsiq.h VSIQ_ACT_SILU_REF):
@@ -280,6 +284,9 @@ _SIGS = {
                                     c_d, c_p], c_int),
     "vsiq_host_adaround_bwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_int, c_int, c_int, c_d,
                                     c_d], c_int),
+    "vsiq_mx_blocks": ([c_i64, c_i64], c_i64),
+    "vsiq_host_mx_fq_fwd_f32": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int], c_int),
+    "vsiq_host_mx_fq_fwd_cols_f32": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int], c_int),
 }
 EXPORTED = tuple(_SIGS)
 

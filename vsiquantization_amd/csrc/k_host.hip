@@ -25,6 +25,7 @@
 
 #include "host_simd.h"
 #include "k_adaround.cuh"
+#include "k_mx.cuh"
 #include "k_observe_hist.cuh"
 #include "k_observe_mse.cuh"
 #include "mean_cascade.cuh"
@@ -943,6 +944,62 @@ int vsiq_host_adaround_bwd_f32(const float *g, const float *w, const float *v, f
   if (!g || !w || !v || !grad_v || !scale || !(beta > 0.0) || lam != lam) return VSIQ_E_ARG;
   ada_chunks(rows, rowlen, scale, zp, nq, zp_round, qmin, qmax, [&](int64_t, int64_t e, const HQP &p) {
     grad_v[e] = ada_grad(g[e], w[e] / p.s + p.z, v[e], p.s, p.z, p.lo, p.hi, lam, beta);
+  });
+  return 0;
+}
+
+// MX block-scaled fake quant (k_mx.cuh's element code; include/vsiq.h states it): blocks of
+// 32 on the pool, each block its maximum pattern, its scale and its elements in order.
+// `step` is the element stride inside a block (1: rows, inner: channel columns).
+static void mx_block(const float *x, float *y, uint8_t *codes, uint8_t *mask, int64_t first, int64_t step, int cnt,
+                     uint8_t *scale, const MxFmt &f) {
+  uint32_t am = 0u;
+  for (int j = 0; j < cnt; ++j) am = std::max(am, f2u(x[first + j * step]) & 0x7fffffffu);
+  const MxScale s = mx_scale(am, f);
+  if (scale) *scale = (uint8_t)s.code;
+  for (int j = 0; j < cnt; ++j) {
+    const int64_t e = first + j * step;
+    const MxElem o = mx_elem<true>(x[e], s, f);
+    y[e] = o.y;
+    if (codes) codes[e] = (uint8_t)o.code;
+    if (mask) mask[e] = o.m;
+  }
+}
+
+int64_t vsiq_mx_blocks(int64_t rows, int64_t rowlen) {
+  if (rows <= 0 || rowlen <= 0) return VSIQ_E_ARG;
+  return rows * mx_row_blocks(rowlen);
+}
+
+int vsiq_host_mx_fq_fwd_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales, uint8_t *mask, int64_t rows,
+                            int64_t rowlen, int fmt) {
+  if (rows <= 0 || rowlen <= 0 || !mx_fmt_ok(fmt) || !x || !y) return VSIQ_E_ARG;
+  const MxFmt f = mx_fmt(fmt);
+  const int64_t nb = mx_row_blocks(rowlen), per = kChunk / 32;
+  Pool::get().run(cdiv(rows * nb, per), [&](int64_t c) {
+    const int64_t b1 = std::min(rows * nb, (c + 1) * per);
+    for (int64_t b = c * per; b < b1; ++b) {
+      const int64_t r = b / nb, k = b % nb;
+      mx_block(x, y, codes, mask, r * rowlen + 32 * k, 1, (int)std::min<int64_t>(32, rowlen - 32 * k),
+               scales ? scales + b : nullptr, f);
+    }
+  });
+  return 0;
+}
+
+int vsiq_host_mx_fq_fwd_cols_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales, uint8_t *mask,
+                                 int64_t outer, int64_t channels, int64_t inner, int fmt) {
+  if (outer <= 0 || channels <= 0 || inner <= 0 || !mx_fmt_ok(fmt) || !x || !y) return VSIQ_E_ARG;
+  if (channels > 0x7fffffffffffffffLL / outer || outer * channels > 0x7fffffffffffffffLL / inner) return VSIQ_E_ARG;
+  const MxFmt f = mx_fmt(fmt);
+  const int64_t cb = cdiv(channels, 32), nb = outer * cb * inner, per = kChunk / 32;
+  Pool::get().run(cdiv(nb, per), [&](int64_t c) {
+    const int64_t b1 = std::min(nb, (c + 1) * per);
+    for (int64_t b = c * per; b < b1; ++b) {   // b = (o * cb + k) * inner + in: the scales' layout
+      const int64_t in = b % inner, ok = b / inner, o = ok / cb, k = ok % cb;
+      mx_block(x, y, codes, mask, (o * channels + 32 * k) * inner + in, inner,
+               (int)std::min<int64_t>(32, channels - 32 * k), scales ? scales + b : nullptr, f);
+    }
   });
   return 0;
 }

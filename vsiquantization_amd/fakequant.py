@@ -16,6 +16,7 @@ eager torch ops in the reference:
   FakeQuantLearnMultiFn    FakeQuantLearnFn over many tensors in one launch each way
   observe_parts/fold_parts deferred-calibration observer (K2p) and its one-launch fold
   observe_parts_out        K2p that also writes act(x): a fused layer's calibration forward (K2o)
+  mx_fake_quant            OCP MX block-scaled fake quant (MXFP4 / MXFP6 / MXFP8), CPU tensors only so far
 
 Every op takes an optional ``act`` ("relu" / "silu", K5): the op is then applied
 to act(x) without materializing it -- the fused layers' F.relu / F.silu before
@@ -1305,3 +1306,126 @@ class AdaRoundFn(torch.autograd.Function):
         gv = adaround_backward(gy, w, V, scale, zero_point, qmin, qmax, axis=axis, lam=lam, beta=beta,
                                zp_round=zp_round)
         return gv, None, None, None, None, None, None, None, None, None
+
+
+# --------------------------------------------------------------------------- MX block scaling
+def _mx_format(fmt):
+    """(VSIQ_MX_* code, bits, exponent bits, mantissa bits, bias) of an element-format name."""
+    try:
+        return H.MX_FORMATS[fmt]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown MX element format {fmt!r} (one of {sorted(H.MX_FORMATS)})") from None
+
+
+def _mx_view(shape, axis):
+    """The host loops' view of blocks along ``axis`` of a contiguous tensor of ``shape``: (rows,
+    rowlen) for the last axis (and for axis 1 of an [N, C] tensor), (outer, channels, inner)
+    for axis 1 of an [N, C, ...] tensor; plus the shape of the scales tensor."""
+    nd = len(shape)
+    if nd == 0:
+        return (1, 1), (1,)
+    ax = axis + nd if axis < 0 else axis
+    n = 1
+    for d in shape:
+        n *= d
+    if n == 0:
+        raise ValueError(f"MX fake quant of an empty tensor (shape {tuple(shape)})")
+    if ax == nd - 1:
+        nb = -(-shape[-1] // 32)
+        return (n // shape[-1], shape[-1]), tuple(shape[:-1]) + (nb,)
+    if ax == 1 and nd > 2:
+        inner = n // (shape[0] * shape[1])
+        return (shape[0], shape[1], inner), (shape[0], -(-shape[1] // 32)) + tuple(shape[2:])
+    raise NotImplementedError(f"MX blocks run along the last axis or axis 1, got axis {axis} of a {nd}-d tensor")
+
+
+def _mx_forward(x, fmt, axis, want_codes, want_mask):
+    """One MX fake-quant call on a contiguous CPU float32 x (the host loops): (y, codes | None,
+    scales | None, mask | None); the mask is one byte per element.  There is no device kernel:
+    a CUDA tensor raises (never a quiet copy to the host)."""
+    code = _mx_format(fmt)[0]
+    if not _host.is_host(x):
+        if x.device.type == "cpu":
+            raise TypeError(f"x: only float32 is supported by the host (CPU) MX fake quant, got {x.dtype}")
+        raise H.VsiqError(f"x is on {x.device}: MX fake quant has no HIP kernel yet and runs on CPU float32 "
+                          "tensors only (the native host loops); nothing is copied to the host behind your back")
+    view, sshape = _mx_view(x.shape, axis)
+    y = torch.empty_like(x)
+    codes = torch.empty(x.shape, dtype=torch.uint8) if want_codes else None
+    scales = torch.empty(sshape, dtype=torch.uint8) if want_codes else None
+    mask = torch.empty(x.shape, dtype=torch.uint8) if want_mask else None
+    _host.mx_fake_quant(x, y, codes, scales, mask, view, code)
+    return y, codes, scales, mask
+
+
+class MXFakeQuantFn(torch.autograd.Function):
+    """MX fake quant with the straight-through gradient: grad_x = g where rounding stayed on
+    the element grid, 0 where it picked the overflow value.  Saves the mask; the backward is
+    the existing STE backward with scale 1 ((mask ? g * 1 : 0) / 1 is g exactly)."""
+
+    @staticmethod
+    def forward(ctx, x, fmt, axis):
+        y, _, _, mask = _mx_forward(x, fmt, axis, False, True)
+        ctx.save_for_backward(mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (mask,) = ctx.saved_tensors
+        return ste_backward(gy.contiguous(), mask, 1.0), None, None
+
+
+def _is_channels_last(x) -> bool:
+    return x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+
+
+def mx_fake_quant(x: torch.Tensor, fmt: str, axis: int = -1, want_codes: bool = False):
+    """OCP MX fake quant (include/vsiq.h, "MX block-scaled fake quantization"): blocks of 32
+    consecutive elements along ``axis`` share one power-of-two scale and every element is
+    rounded to the 4-, 6- or 8-bit float ``fmt`` ("fp4_e2m1", "fp6_e2m3", "fp6_e3m2",
+    "fp8_e4m3", "fp8_e5m2").  CPU float32 tensors only, on the native host loops (there is no
+    HIP kernel for it yet: a CUDA tensor raises VsiqError).
+    axis=-1: rows are everything before the last dim; axis=1 of an [N, C, ...] tensor: blocks
+    along the channels (an [N, C] tensor: its rows).  Differentiable in x (MXFakeQuantFn).
+    Returns y, or (y, codes uint8 like x, scales uint8: x's shape with ``axis`` cut to its
+    block count) with ``want_codes``."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"x must be a torch.Tensor, got {type(x).__name__}")
+    _mx_format(fmt)
+    nd = x.dim()
+    if nd and not -nd <= axis < nd:
+        raise NotImplementedError(f"MX blocks run along the last axis or axis 1, got axis {axis} of a {nd}-d tensor")
+    if axis % max(nd, 1) == 1 and _is_channels_last(x):   # NHWC memory: the channels are its rows
+        out = mx_fake_quant(x.permute(0, 2, 3, 1), fmt, -1, want_codes)
+        return tuple(t.permute(0, 3, 1, 2) for t in out) if want_codes else out.permute(0, 3, 1, 2)
+    x = x.contiguous()
+    if want_codes:
+        y, codes, scales, _ = _mx_forward(x.detach(), fmt, axis, True, False)
+        return y, codes, scales
+    if x.requires_grad and torch.is_grad_enabled():
+        return MXFakeQuantFn.apply(x, fmt, axis)
+    return _mx_forward(x, fmt, axis, False, False)[0]
+
+
+def mx_dequant(codes: torch.Tensor, scales: torch.Tensor, fmt: str, axis: int = -1, dtype=torch.float32):
+    """The inverse of mx_fake_quant(..., want_codes=True): y = table[code] * 2^(scale - 127),
+    a 2^bits-entry lookup times the block's power of two (built from its exponent bits, so
+    exact), in eager torch (not a hot path).  A scale byte of 255 gives NaN."""
+    _, bits, ebits, mbits, bias = _mx_format(fmt)
+    dev = codes.device
+    c = torch.arange(1 << bits, dtype=torch.int32)
+    eb, m = (c >> mbits) & ((1 << ebits) - 1), c & ((1 << mbits) - 1)
+    mag = torch.where(eb == 0, m.double() * 2.0 ** (1 - bias - mbits),
+                      (1.0 + m.double() / (1 << mbits)) * torch.pow(2.0, (eb - bias).double()))
+    table = torch.where((c >> (bits - 1)) == 1, -mag, mag).to(torch.float32).to(dev)
+    s = scales.to(torch.int32)
+    x2 = torch.where(s == 0, torch.full_like(s, 0x00400000), s << 23).view(torch.float32)   # 2^(s - 127)
+    nd = codes.dim()
+    ax = axis + nd if axis < 0 else axis
+    if not (ax == nd - 1 or (ax == 1 and nd > 2)):
+        raise NotImplementedError(f"MX blocks run along the last axis or axis 1, got axis {axis} of a {nd}-d tensor")
+    x2 = x2.repeat_interleave(32, dim=ax).narrow(ax, 0, codes.shape[ax])
+    nan_block = (s == 255).repeat_interleave(32, dim=ax).narrow(ax, 0, codes.shape[ax])
+    y = table[codes.long() & ((1 << bits) - 1)] * x2
+    y = torch.where(nan_block, torch.full_like(y, float("nan")), y)
+    return y if dtype == torch.float32 else y.to(dtype)

@@ -331,6 +331,20 @@ def adaround_backward(g, w, V, gv, rows, rowlen, s, z, nq, zp_round, qmin, qmax,
     H.check(rc, "vsiq_host_adaround_bwd_f32")
 
 
+# --------------------------------------------------------------------------- MX
+def mx_fake_quant(x, y, codes, scales, mask, view, fmt):
+    """Host leg of fakequant.mx_fake_quant (which has checked the arguments and made the
+    outputs; mask: one byte per element): ``view`` is (rows, rowlen) or (outer, channels, inner)."""
+    if len(view) == 2:
+        rc = H.lib().vsiq_host_mx_fq_fwd_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(scales), H.ptr(mask),
+                                             _i64(view[0]), _i64(view[1]), int(fmt))
+        H.check(rc, "vsiq_host_mx_fq_fwd_f32")
+    else:
+        rc = H.lib().vsiq_host_mx_fq_fwd_cols_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(scales), H.ptr(mask),
+                                                  _i64(view[0]), _i64(view[1]), _i64(view[2]), int(fmt))
+        H.check(rc, "vsiq_host_mx_fq_fwd_cols_f32")
+
+
 def threads() -> int:
     """Host threads the CPU path uses (VSIQ_HOST_THREADS, else the CPUs this process may use)."""
     return int(H.lib().vsiq_host_threads())
@@ -343,5 +357,5 @@ def simd() -> bool:
 
 __all__ = ["is_host", "fake_quant", "ste_backward", "lsq_backward", "observe_tensor", "observe_percentile",
            "observe_mse", "torch_mean", "pc_observe_fq", "pc_observe_mse", "pc_fake_quant", "pc_ste_backward",
-           "pc_lsq_backward", "quantize_pack", "unpack_dequant", "adaround_forward", "adaround_backward", "threads",
+           "pc_lsq_backward", "quantize_pack", "unpack_dequant", "adaround_forward", "adaround_backward", "mx_fake_quant", "threads",
            "simd"]

@@ -21,6 +21,10 @@ class FakeQuantize(nn.Module):
                                                     w_symmetric, is_learning_scale=True)
         self.activation_quantizer = QuantizationManager(quantizer_a_name, observer_a_name, bits_a,
                                                         a_symmetric, is_learning_scale=True)
+        if getattr(self.activation_quantizer.quantizer, "self_scaled", False):
+            # MX blocks of an activation run along its channels, the axis the next layer's
+            # dot product runs along ([N, C, ...]; an [N, C] tensor: its rows)
+            self.activation_quantizer.quantizer.block_axis = 1
         self.bits_w = bits_w
         self.bits_a = bits_a
         self.quantize_out = quantize_out

@@ -431,6 +431,15 @@ class QuantizationManager(nn.Module):
         ``act`` ("relu" / "silu"): the layer's activation, applied to ``x`` first; with
         this package's kernels it is fused into the observer and the fake quant (K5); a
         SiLU uses the reference layout recorded with this manager's qparams (silu_layout)."""
+        if getattr(self.quantizer, "self_scaled", False):
+            # a quantizer that scales every block by its own maximum (MXQuantizer): nothing
+            # to observe, record or defer; the activation runs unfused in front of it
+            self._join()
+            if act is not None:
+                x = _activation(x, act)
+            if self.is_quantize:
+                return self.quantizer.quantize(x, self.scale, self.zero_point, self.is_learning_scale)
+            return x
         if act is not None:
             act = self._silu_act(act)
         if self.is_quantize or self.is_learning_scale:
@@ -490,6 +499,20 @@ class QuantizationManager(nn.Module):
         from ..fakequant import quantize_pack
         s, z, qmin, qmax, axis, zp_round = self.current_grid(x, "export_packed")
         return quantize_pack(x.detach(), s, z, qmin, qmax, axis=axis, zp_round=zp_round)
+
+    def export_mx(self, x):
+        """``x`` as MX element codes and block scales: (codes uint8 like x, scales uint8, the
+        element-format name) of what ``quantize(x)`` computes under a self-scaled quantizer
+        (MXQuantizer); fakequant.mx_dequant(codes, scales, fmt, axis=quantizer.block_axis)
+        reproduces it.  Nothing changes; the activation is not applied."""
+        q = self.quantizer
+        if not getattr(q, "self_scaled", False):
+            raise NotImplementedError(f"export_mx supports MXQuantizer, not {type(q).__name__}")
+        from ..fakequant import mx_fake_quant
+        self._join()
+        axis = q.block_axis if x.dim() >= 2 else -1
+        _, codes, scales = mx_fake_quant(x.detach(), q.elem_format, axis=axis, want_codes=True)
+        return codes, scales, q.elem_format
 
     def current_grid(self, x, what: str = "current_grid"):
         """(scale, zero_point, qmin, qmax, axis, zp_round) that ``quantize(x)`` in eval applies
@@ -617,6 +640,8 @@ class QuantizationManager(nn.Module):
         The reference creates it on the CPU and relies on a later ``model.to(device)``; here
         it is created where the observer state lives, so a model that is not moved again
         does not read its scale back to the host on every call (and stays graph-capturable)."""
+        if getattr(self.quantizer, "self_scaled", False):
+            return   # block scales come from the data: nothing to learn
         self._join()
         dev = self._home_device()
         s = self.scale
@@ -643,6 +668,8 @@ class QuantizationManager(nn.Module):
 
     def init_scaling_factor_for_learning(self):
         """scale = 2 * mean(mean_abs_x) / sqrt(2^(b-1) - 1)  (qm.py:105-112)."""
+        if getattr(self.quantizer, "self_scaled", False):
+            return
         self.scale = 2 * np.mean(self.mean_abs_x) / np.sqrt(2 ** (self.bits_width - 1) - 1)
 
     def winsorized_mean(self, x, lower=5, upper=95, sample_size=1000000):
