@@ -423,6 +423,44 @@ int vsiq_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t n,
                      const double *scale_dev, int64_t rowlen, double scale_host, void *stream);
 
 /*
+ * Group-wise (per-group) weight quantization ("w4 g128"; csrc/k_pg.hip).
+ *
+ * Layout.  x (fp32, contiguous) is viewed as `rows` rows of `rowlen` elements, K3's view.
+ * With `group` G in {32, 64, 128, 256} a row has ngr = ceil(rowlen / G) groups; group j of
+ * row r covers elements [j*G, min((j+1)*G, rowlen)) of that row: groups restart at every
+ * row and the last group of a row may be short.  Every per-group array (run_min, run_max
+ * fp32; scale, zp f64) is [rows, ngr], group (r, j) at index r*ngr + j.  y and codes have
+ * x's layout.  The mask is the 1-bit mask of the WHOLE tensor in the (rows, rowlen) layout
+ * stated at the top of this file -- vsiq_mask_words(rows, rowlen) words, one bit per
+ * element, not one padded row per group -- so it is the mask vsiq_pc_observe_fq_f32 /
+ * vsiq_ste_bwd_f32 would use for the same tensor.
+ *
+ * vsiq_pg_observe_fq_f32: every group is processed exactly as vsiq_pc_observe_fq_f32
+ * processes a row holding that group's elements: the group's fp32 min / max, the running
+ * update of (run_min, run_max)[r, j] (zeros = fresh observers; a group holding a NaN changes
+ * nothing), the f64 qparams into (scale_out, zp_out)[r, j], and y / codes / mask from the
+ * same element function.  One launch, one read and one write of every element.
+ * y == NULL observes only (codes / mask must then be NULL too); codes and mask are nullable.
+ * Errors as vsiq_pc_observe_fq_f32 (there is no row_stats); a group outside {32, 64, 128,
+ * 256} is VSIQ_E_ARG, as is a tensor of more than 2^31 - 1 256-element row chunks.
+ * vsiq_pg_fq_fwd_f32: the same forward with given [rows, ngr] f64 scale / zp (both
+ * required); zp_round != 0 applies clamp(rint(zp)) first, as vsiq_pc_fq_fwd_f32.
+ * vsiq_pg_ste_bwd_f32: gx = (mask ? g*s : 0) / s with s = fp32(scale[r, j]), vsiq_ste_bwd_f32's
+ * formula with the element's group's scale.
+ * rowlen % 4 == 0 with 16-byte aligned tensors (codes: 4-byte) takes the vector path; any
+ * other row length or alignment a per-element path with the same results.  None of the
+ * three allocates, synchronises or uses a workspace: capturable into a HIP graph.
+ */
+int vsiq_pg_observe_fq_f32(const float *x, float *y, void *codes, uint64_t *mask, int64_t rows, int64_t rowlen,
+                           int64_t group, float *run_min, float *run_max, double *scale_out, double *zp_out,
+                           int symmetric, int qmin, int qmax, double qden, double eps, void *stream);
+int vsiq_pg_fq_fwd_f32(const float *x, float *y, void *codes, uint64_t *mask, int64_t rows, int64_t rowlen,
+                       int64_t group, const double *scale, const double *zp, int zp_round, int qmin, int qmax,
+                       void *stream);
+int vsiq_pg_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t rows, int64_t rowlen,
+                        int64_t group, const double *scale, void *stream);
+
+/*
  * Learnable (LSQ) backward (K4): grad_x plus the scale / zero-point gradients.
  * Replaces autograd over uniform.py:47-56 (ScaleGradient, RoundStraightThrough,
  * clamp, div, mul; uniform.py:242-271):
@@ -953,6 +991,18 @@ int vsiq_host_pc_ste_bwd_f32(const float *g, const uint8_t *mask, float *gx, int
 int vsiq_host_pc_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen,
                              const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,
                              double *grad_scale_out, double *grad_zp_out);
+/* Group-wise on the host (the vsiq_pg_* layout: ngr = ceil(rowlen / group) groups per row,
+ * per-group arrays [rows, ngr]): each group is the per-tensor host call above on the group's
+ * elements alone, i.e. what the vsiq_host_pc_* calls do with a row that holds them; mask one
+ * byte per element in x's layout, no codes; y NULL: observe only.  group outside {32, 64,
+ * 128, 256}: VSIQ_E_ARG. */
+int vsiq_host_pg_observe_fq_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen, int64_t group,
+                                float *run_min, float *run_max, double *scale_out, double *zp_out, int symmetric,
+                                double qden, double eps, int qmin, int qmax);
+int vsiq_host_pg_fq_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen, int64_t group,
+                            const double *scale, const double *zp, int zp_round, int qmin, int qmax);
+int vsiq_host_pg_ste_bwd_f32(const float *g, const uint8_t *mask, float *gx, int64_t rows, int64_t rowlen,
+                             int64_t group, const double *scale);
 /* Per-channel along axis 1 ([N, C, ...] activations, LSQFakeQuantize's broadcast of
  * [1, C, 1, ...] parameters, quantizers/lsq_module.py:141-143) on the host, in the device
  * ABI's vsiq_pcm_* layout: rows = N * channels rows of rowlen elements, row r in channel

@@ -9,6 +9,7 @@ Importing the package registers the quantizer/observer classes by name in
   PerChannelUniformQuantizer, PerChannelMinMaxObserver  (per-channel, axis 0)
   PercentileObserver, MSEObserver                   (calibrators that clip the min / max range)
   PerChannelMSEObserver                             (MSEObserver's search on every out-channel row)
+  PerGroupUniformQuantizer, PerGroupMinMaxObserver  (group-wise weights, groups of 32..256: "w4 g128")
   MXQuantizer                                       (OCP MX block scaling: MXFP4 / MXFP6 / MXFP8)
 
 plus ``LSQFakeQuantize`` (quantizers/lsq_module.py, the torch.ao-based LSQ module).
@@ -30,6 +31,8 @@ from .observers.per_channel import PerChannelMinMaxObserver  # noqa: F401
 from .observers.percentile import PercentileObserver  # noqa: F401
 from .observers.mse import MSEObserver  # noqa: F401
 from .observers.per_channel_mse import PerChannelMSEObserver  # noqa: F401
+from .observers.per_group import PerGroupMinMaxObserver  # noqa: F401
+from .quantizers.per_group import PerGroupUniformQuantizer  # noqa: F401
 from .quantizers.quantization_manager import QuantizationManager  # noqa: F401
 from .quantizers.fake_quantize import FakeQuantize  # noqa: F401
 from .quantizers.lsq_module import LSQFakeQuantize  # noqa: F401
@@ -41,6 +44,7 @@ from .fakequant import adaround_backward, adaround_forward  # noqa: F401
 from .quantizers.adaround import AdaRoundWeight  # noqa: F401
 from .utils.adaround import adaround_layer, adaround_model  # noqa: F401
 from .fakequant import mx_dequant, mx_fake_quant  # noqa: F401
+from .fakequant import per_group_fake_quant, per_group_observe_fq, pg_ste_backward  # noqa: F401
 from .quantizers.mx import MXQuantizer  # noqa: F401
 from .utils.quantize_manager import (disable_model_launches, enable_model_launches,  # noqa: F401
                                      model_launches_enabled)

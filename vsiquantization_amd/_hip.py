@@ -51,6 +51,7 @@ DT_F32, DT_BF16, DT_F16 = 0, 1, 2   # VSIQ_DT_*: the element type of the typed (
 # bits, mantissa bits, exponent bias)
 MX_FORMATS = {"fp4_e2m1": (0, 4, 2, 1, 1), "fp6_e2m3": (1, 6, 2, 3, 1), "fp6_e3m2": (2, 6, 3, 2, 3),
               "fp8_e4m3": (3, 8, 4, 3, 7), "fp8_e5m2": (4, 8, 5, 2, 15)}
+PG_GROUPS = (32, 64, 128, 256)   # group sizes of the group-wise (vsiq_pg_*) entry points
 ACT_CODES = {None: ACT_NONE, "none": ACT_NONE, "relu": ACT_RELU, "silu": ACT_SILU}
 
 # SiLU bit for bit as torch's CPU kernel on this host (include/vsiq.h VSIQ_ACT_SILU_REF):
@@ -253,6 +254,14 @@ _SIGS = {
                                   c_int),
     "vsiq_host_pc_lsq_bwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int, c_d, c_p, c_p],
                                  c_int),
+    "vsiq_pg_observe_fq_f32": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_int, c_int, c_int,
+                                c_d, c_d, c_p], c_int),
+    "vsiq_pg_fq_fwd_f32": ([c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int, c_p], c_int),
+    "vsiq_pg_ste_bwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p], c_int),
+    "vsiq_host_pg_observe_fq_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_int, c_d, c_d, c_int,
+                                     c_int], c_int),
+    "vsiq_host_pg_fq_fwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int], c_int),
+    "vsiq_host_pg_ste_bwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p], c_int),
     "vsiq_host_threads": ([], c_int),
     "vsiq_host_simd": ([], c_int),
     "vsiq_act_fwd_f32": ([c_p, c_p, c_i64, c_int, c_p], c_int),
@@ -469,6 +478,30 @@ def pc_observe_buffers(x: torch.Tensor, C: int, run_min, run_max, quantize: bool
     zp = torch.empty(C, dtype=torch.float64, device=dev)
     rstats = torch.empty(C, 3, dtype=torch.float64, device=dev) if want_row_stats else None
     return run_min, run_max, y, scale, zp, rstats
+
+
+def pg_observe_buffers(x: torch.Tensor, rows: int, ngr: int, run_min, run_max, quantize: bool):
+    """What a group-wise observe of x works on, on x's device: the per-group running state
+    (fresh 0/0 where none is given; ValueError unless fp32, contiguous, on x's device and of
+    rows * ngr entries) and its outputs (run_min, run_max, y | None, scale f64[rows, ngr],
+    zp f64[rows, ngr])."""
+    dev = x.device
+    if run_min is None or run_max is None:
+        state = torch.zeros(2, rows, ngr, dtype=torch.float32, device=dev)
+        given = (run_min, run_max)
+        run_min = state[0] if run_min is None else run_min
+        run_max = state[1] if run_max is None else run_max
+    else:
+        given = (run_min, run_max)
+    for r in given:   # the kernel writes rows * ngr floats through these pointers
+        if r is not None and (r.numel() != rows * ngr or r.dtype != torch.float32 or r.device != dev
+                              or not r.is_contiguous()):
+            raise ValueError(f"per-group running state must be contiguous float32 on {dev} with {rows} x {ngr} "
+                             f"entries, got {r.dtype} {tuple(r.shape)} on {r.device}")
+    y = torch.empty_like(x) if quantize else None
+    scale = torch.empty(rows, ngr, dtype=torch.float64, device=dev)
+    zp = torch.empty(rows, ngr, dtype=torch.float64, device=dev)
+    return run_min, run_max, y, scale, zp
 
 
 def set_tuning(key: int, value: int):

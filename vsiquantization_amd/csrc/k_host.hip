@@ -28,6 +28,7 @@
 #include "k_mx.cuh"
 #include "k_observe_hist.cuh"
 #include "k_observe_mse.cuh"
+#include "k_pg.cuh"
 #include "mean_cascade.cuh"
 #include "vsiq_common.cuh"
 
@@ -664,6 +665,72 @@ int vsiq_host_pc_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t 
                              double *grad_scale_out, double *grad_zp_out) {
   return vsiq_host_pcm_lsq_bwd_f32(g, x, gx, rows, rowlen, rows, scale, zp, zp_learn, qmin, qmax, gscale,
                                    grad_scale_out, grad_zp_out);
+}
+
+// Group-wise (k_pg.cuh's view: ngr = ceil(rowlen / group) groups per row, the last one of a
+// row possibly short, qparams at [r * ngr + j]): every group is the per-tensor host call on
+// the group's elements alone -- exactly what vsiq_host_pc_observe_fq_f32 / _pc_fq_fwd_f32 /
+// _pc_ste_bwd_f32 do with a row that holds them.  Rows run on the pool, a row's groups in order.
+// vsiq_host_observe_f32 also sums each group's mean|x| / mean / std record, which nothing here
+// reads: wasted work per 32 to 256 elements, the price of building on the existing host calls.
+int vsiq_host_pg_observe_fq_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen, int64_t group,
+                                float *run_min, float *run_max, double *scale_out, double *zp_out, int symmetric,
+                                double qden, double eps, int qmin, int qmax) {
+  if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || qmin > qmax) return VSIQ_E_ARG;
+  if (rows == 0) return 0;   // as the device entry
+  if (!x || !run_min || !run_max || !scale_out || !zp_out || (!y && mask)) return VSIQ_E_ARG;
+  const int64_t ngr = pg_groups_per_row(rowlen, group);
+  std::atomic<int> rc{0};
+  Pool::get().run(rows, [&](int64_t r) {
+    for (int64_t j = 0; j < ngr; ++j) {
+      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group), q = r * ngr + j;
+      float st[2] = {run_min[q], run_max[q]};
+      double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN];
+      int e = vsiq_host_observe_f32(x + o, len, kActNone, stats, st, qp, symmetric, qden, eps);
+      run_min[q] = st[0];
+      run_max[q] = st[1];
+      scale_out[q] = qp[VSIQ_QP_SCALE];
+      zp_out[q] = qp[VSIQ_QP_ZP];
+      if (!e && y)
+        e = vsiq_host_fq_fwd_f32(x + o, y + o, nullptr, mask ? mask + o : nullptr, len, kActNone, qp, 0.0, 0.0, 0, 0,
+                                 qmin, qmax);
+      if (e) rc.store(e);
+    }
+  });
+  return rc.load();
+}
+
+int vsiq_host_pg_fq_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen, int64_t group,
+                            const double *scale, const double *zp, int zp_round, int qmin, int qmax) {
+  if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || (rows > 0 && (!x || !y || !scale || !zp)) || qmin > qmax)
+    return VSIQ_E_ARG;
+  const int64_t ngr = pg_groups_per_row(rowlen, group);
+  std::atomic<int> rc{0};
+  Pool::get().run(rows, [&](int64_t r) {
+    for (int64_t j = 0; j < ngr; ++j) {
+      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group), q = r * ngr + j;
+      const int e = vsiq_host_fq_fwd_f32(x + o, y + o, nullptr, mask ? mask + o : nullptr, len, kActNone, nullptr,
+                                         scale[q], zp[q], zp_round, 0, qmin, qmax);
+      if (e) rc.store(e);
+    }
+  });
+  return rc.load();
+}
+
+int vsiq_host_pg_ste_bwd_f32(const float *g, const uint8_t *mask, float *gx, int64_t rows, int64_t rowlen,
+                             int64_t group, const double *scale) {
+  if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || (rows > 0 && (!g || !mask || !gx || !scale)))
+    return VSIQ_E_ARG;
+  const int64_t ngr = pg_groups_per_row(rowlen, group);
+  std::atomic<int> rc{0};
+  Pool::get().run(rows, [&](int64_t r) {
+    for (int64_t j = 0; j < ngr; ++j) {
+      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group);
+      const int e = vsiq_host_ste_bwd_f32(g + o, mask + o, nullptr, gx + o, len, kActNone, scale[r * ngr + j]);
+      if (e) rc.store(e);
+    }
+  });
+  return rc.load();
 }
 
 // Axis 1 ([N, C, ...]): row r = n * channels + c in channel c, each row the per-tensor host

@@ -11,6 +11,7 @@ eager torch ops in the reference:
   fake_quant               quantizers/uniform.py:54-55,95   (K1)
   observe_tensor           observers/minmax.py:32-88 + quantization_manager.py:66-68 (K2)
   per_channel_observe_fq   per-channel MinMax + UniformQuantizer (K3)
+  per_group_observe_fq     the same on every group of 32..256 consecutive elements of a row (k_pg.hip)
   FakeQuantFixedFn         autograd of uniform.py:55,95 with fixed qparams (STE)
   FakeQuantLearnFn         autograd of uniform.py:47-56 (LSQ: ScaleGradient, STE) (K4)
   FakeQuantLearnMultiFn    FakeQuantLearnFn over many tensors in one launch each way
@@ -1038,6 +1039,159 @@ class PerChannelObserveMSEFn(torch.autograd.Function):
     def backward(ctx, gy, _gs, _gz, _gr, _ge, _gp):
         mask, scale = ctx.saved_tensors
         return pc_ste_backward(gy, mask, scale), None, None, None, None, None, None, None, None, None
+
+
+# --------------------------------------------------------------------------- per-group
+def check_group_size(group_size) -> int:
+    """``group_size`` as an int, or ValueError: one of H.PG_GROUPS (32, 64, 128, 256)."""
+    if group_size not in H.PG_GROUPS or not isinstance(group_size, (int, np.integer)):   # 128.0, "128", True: no
+        raise ValueError(f"per-group quantization: group_size must be one of {H.PG_GROUPS}, got {group_size!r}")
+    return int(group_size)
+
+
+def _pg_input(x, what="x"):
+    """(contiguous fp32 tensor, is_host) of a per-group op's tensor; TypeError for anything but
+    float32 (the 16-bit kernels are per-tensor only)."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{what} must be a torch.Tensor, got {type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"per-group quantization: {what} must be float32, got {x.dtype}")
+    kind = x.device.type
+    if kind == "cuda" or kind == "cpu":
+        return x.contiguous(), kind == "cpu"
+    return H.require_device_f32(x, what), False   # raises: neither the GPU nor the host path
+
+
+def _pg_view(x, group):
+    """(rows, rowlen, ngr) of the group-wise view of x: axis-0 rows as K3, ngr groups per row."""
+    rows = x.shape[0] if x.dim() > 0 else 1
+    if rows == 0 or x.numel() == 0:
+        raise H.empty_error()
+    rowlen = x.numel() // rows
+    return rows, rowlen, -(-rowlen // group)
+
+
+def _pg_f64(v, rows, ngr, dev, what):
+    """v as a contiguous f64 [rows, ngr] tensor on dev (any float dtype, any shape of rows * ngr entries)."""
+    if not isinstance(v, torch.Tensor):
+        raise TypeError(f"per-group {what} must be a [rows, groups] tensor, got {type(v).__name__}")
+    t = v.detach().to(dev, torch.float64)
+    if t.numel() != rows * ngr:
+        raise ValueError(f"per-group {what} has {t.numel()} entries, the tensor has {rows} x {ngr} groups")
+    return t.reshape(rows, ngr).contiguous()
+
+
+def per_group_observe_fq(x: torch.Tensor, *, group_size: int, symmetric: bool, qmin: int, qmax: int,
+                         obs_bits: int = 8, eps: float = 1e-8, run_min=None, run_max=None,
+                         quantize: bool = True, want_mask: bool = False, want_codes: bool = False):
+    """Fused group-wise MinMax observe + f64 qparams + fake quant in one launch and one read of
+    x (csrc/k_pg.hip).  x is viewed as x.shape[0] rows (K3's view); every run of ``group_size``
+    (32 / 64 / 128 / 256) consecutive elements of a row -- the last one of a row may be short --
+    is observed and quantized exactly as per_channel_observe_fq treats a row holding those
+    elements, on its own running (run_min, run_max)[row, group] (fp32 [rows, ngr]; fresh 0/0
+    when None; updated in place).
+
+    quantize=False observes only (y is None).  Returns dict(y, scale f64[rows, ngr], zp
+    f64[rows, ngr], run_min, run_max, mask, codes); the mask is the whole tensor's 1-bit
+    (rows, rowlen) mask (include/vsiq.h).  A CPU tensor takes the native host loops
+    (host.pg_observe_fq; byte mask; codes are a device output only)."""
+    group = check_group_size(group_size)
+    x, host = _pg_input(x)
+    if host:
+        if want_codes:
+            raise NotImplementedError("per_group_observe_fq: integer codes are written by the HIP kernel only; "
+                                      "the host loops have none")
+        return _host.pg_observe_fq(x, group, symmetric=symmetric, qmin=qmin, qmax=qmax, obs_bits=obs_bits, eps=eps,
+                                   run_min=run_min, run_max=run_max, quantize=quantize, want_mask=want_mask)
+    dev = x.device
+    rows, rowlen, ngr = _pg_view(x, group)
+    run_min, run_max, y, scale, zp = H.pg_observe_buffers(x, rows, ngr, run_min, run_max, quantize)
+    mask = H.mask_buffer(rows, rowlen, dev) if (want_mask and quantize) else None
+    codes = H.codes_buffer(x.shape, qmin, dev) if (want_codes and quantize) else None
+    rc = H.lib().vsiq_pg_observe_fq_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(rows), _i64(rowlen),
+                                        _i64(group), H.ptr(run_min), H.ptr(run_max), H.ptr(scale), H.ptr(zp),
+                                        int(bool(symmetric)), int(qmin), int(qmax), qden(symmetric, obs_bits, eps),
+                                        float(eps), H.stream_of(dev))
+    H.check(rc, "vsiq_pg_observe_fq_f32")
+    return dict(y=y, scale=scale, zp=zp, run_min=run_min, run_max=run_max, mask=mask, codes=codes)
+
+
+def per_group_fake_quant(x, scale, zp, qmin, qmax, *, group_size, zp_round=False, want_mask=False,
+                         want_codes=False):
+    """Group-wise fake quant with given [rows, ngr] qparams (per_group_observe_fq's layout; any
+    float dtype).  Returns (y, mask | None, codes | None).  A CPU tensor takes the native host
+    loops (host.pg_fake_quant; byte mask, no codes)."""
+    group = check_group_size(group_size)
+    x, host = _pg_input(x)
+    rows, rowlen, ngr = _pg_view(x, group)
+    s = _pg_f64(scale, rows, ngr, x.device, "scale")
+    z = _pg_f64(zp, rows, ngr, x.device, "zero point")
+    if host:
+        if want_codes:
+            raise NotImplementedError("per_group_fake_quant: integer codes are written by the HIP kernel only; "
+                                      "the host loops have none")
+        return (*_host.pg_fake_quant(x, s, z, group, qmin, qmax, zp_round=zp_round, want_mask=want_mask), None)
+    dev = x.device
+    y = torch.empty_like(x)
+    mask = H.mask_buffer(rows, rowlen, dev) if want_mask else None
+    codes = H.codes_buffer(x.shape, qmin, dev) if want_codes else None
+    rc = H.lib().vsiq_pg_fq_fwd_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(rows), _i64(rowlen),
+                                    _i64(group), H.ptr(s), H.ptr(z), int(bool(zp_round)), int(qmin), int(qmax),
+                                    H.stream_of(dev))
+    H.check(rc, "vsiq_pg_fq_fwd_f32")
+    return y, mask, codes
+
+
+def pg_ste_backward(g, mask, scale, group_size):
+    """The group-wise STE backward: gx = (mask ? g*s : 0) / s with s = fp32(scale[row, group]) of
+    each element's group; ``mask`` as the forward on g's side wrote it (device: the 1-bit
+    words; CPU: one byte per element)."""
+    group = check_group_size(group_size)
+    g, host = _pg_input(g, "grad_output")
+    rows, rowlen, ngr = _pg_view(g, group)
+    s = _pg_f64(scale, rows, ngr, g.device, "scale")
+    if host:
+        return _host.pg_ste_backward(g, mask, s, group)
+    gx = torch.empty_like(g)
+    rc = H.lib().vsiq_pg_ste_bwd_f32(H.ptr(g), H.ptr(mask), H.ptr(gx), _i64(rows), _i64(rowlen), _i64(group),
+                                     H.ptr(s), H.stream_of(g.device))
+    H.check(rc, "vsiq_pg_ste_bwd_f32")
+    return gx
+
+
+class PerGroupObserveFQFn(torch.autograd.Function):
+    """per_group_observe_fq with the STE backward (each element uses fp32(scale) of its group).
+    Returns (y, scale, zp)."""
+
+    @staticmethod
+    def forward(ctx, x, group_size, symmetric, qmin, qmax, obs_bits, eps, run_min, run_max):
+        r = per_group_observe_fq(x, group_size=group_size, symmetric=symmetric, qmin=qmin, qmax=qmax,
+                                 obs_bits=obs_bits, eps=eps, run_min=run_min, run_max=run_max, want_mask=True)
+        ctx.save_for_backward(r["mask"], r["scale"])
+        ctx.group = group_size
+        ctx.mark_non_differentiable(r["scale"], r["zp"])
+        return r["y"], r["scale"], r["zp"]
+
+    @staticmethod
+    def backward(ctx, gy, _gs, _gz):
+        mask, scale = ctx.saved_tensors
+        return pg_ste_backward(gy, mask, scale, ctx.group), None, None, None, None, None, None, None, None
+
+
+class PerGroupFQFn(torch.autograd.Function):
+    """Group-wise fake quant with given [rows, ngr] qparams and the STE backward."""
+
+    @staticmethod
+    def forward(ctx, x, scale, zp, qmin, qmax, group_size):
+        y, mask, _ = per_group_fake_quant(x, scale, zp, qmin, qmax, group_size=group_size, want_mask=True)
+        ctx.save_for_backward(mask, scale.detach().to(x.device, torch.float64))
+        ctx.group = group_size
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        mask, scale = ctx.saved_tensors
+        return pg_ste_backward(gy, mask, scale, ctx.group), None, None, None, None, None
 
 
 # --------------------------------------------------------------------------- export

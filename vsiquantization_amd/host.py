@@ -269,6 +269,49 @@ def pc_ste_backward(g, mask, scale, axis=0):
     return gx
 
 
+def pg_observe_fq(x, group, *, symmetric, qmin, qmax, obs_bits=8, eps=1e-8, run_min=None, run_max=None,
+                  quantize=True, want_mask=False):
+    """Host counterpart of fakequant.per_group_observe_fq (which has checked ``group``): each
+    group of ``group`` consecutive elements of a row observed on its own running state and
+    fake-quantized with its own f64 qparams.  Same dict as the device function (byte mask, no codes)."""
+    x = _f32(x)
+    rows, rowlen = _rows(x)
+    ngr = -(-rowlen // group)
+    run_min, run_max, y, scale, zp = H.pg_observe_buffers(x, rows, ngr, run_min, run_max, quantize)
+    _check_state(run_min, run_max)
+    mask = torch.empty(x.shape, dtype=torch.uint8) if (want_mask and quantize) else None
+    rc = H.lib().vsiq_host_pg_observe_fq_f32(H.ptr(x), H.ptr(y), H.ptr(mask), _i64(rows), _i64(rowlen), _i64(group),
+                                             H.ptr(run_min), H.ptr(run_max), H.ptr(scale), H.ptr(zp),
+                                             int(bool(symmetric)), qden(symmetric, obs_bits, eps), float(eps),
+                                             int(qmin), int(qmax))
+    H.check(rc, "vsiq_host_pg_observe_fq_f32")
+    return dict(y=y, scale=scale, zp=zp, run_min=run_min, run_max=run_max, mask=mask, codes=None)
+
+
+def pg_fake_quant(x, scale, zp, group, qmin, qmax, *, zp_round=False, want_mask=False):
+    """Group-wise fake quant with given [rows, ngr] f64 CPU qparams on the host: (y, mask | None)."""
+    x = _f32(x)
+    rows, rowlen = _rows(x)
+    y = torch.empty_like(x)
+    mask = torch.empty(x.shape, dtype=torch.uint8) if want_mask else None
+    rc = H.lib().vsiq_host_pg_fq_fwd_f32(H.ptr(x), H.ptr(y), H.ptr(mask), _i64(rows), _i64(rowlen), _i64(group),
+                                         H.ptr(scale), H.ptr(zp), int(bool(zp_round)), int(qmin), int(qmax))
+    H.check(rc, "vsiq_host_pg_fq_fwd_f32")
+    return y, mask
+
+
+def pg_ste_backward(g, mask, scale, group):
+    """Host counterpart of fakequant.pg_ste_backward (``mask``: pg_fake_quant's bytes; ``scale``
+    f64 [rows, ngr] on the CPU)."""
+    g = _f32(g, "grad_output")
+    rows, rowlen = _rows(g)
+    gx = torch.empty_like(g)
+    rc = H.lib().vsiq_host_pg_ste_bwd_f32(H.ptr(g), H.ptr(mask), H.ptr(gx), _i64(rows), _i64(rowlen), _i64(group),
+                                          H.ptr(scale))
+    H.check(rc, "vsiq_host_pg_ste_bwd_f32")
+    return gx
+
+
 def pc_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, axis=0):
     """Host counterpart of fakequant.pc_lsq_backward (``axis`` 0: [C, ...] weights, 1:
     [N, C, ...] activations -- LSQFakeQuantize): each row the per-tensor learnable host

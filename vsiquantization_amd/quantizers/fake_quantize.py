@@ -21,6 +21,10 @@ class FakeQuantize(nn.Module):
                                                     w_symmetric, is_learning_scale=True)
         self.activation_quantizer = QuantizationManager(quantizer_a_name, observer_a_name, bits_a,
                                                         a_symmetric, is_learning_scale=True)
+        for part in (self.activation_quantizer.quantizer, self.activation_quantizer.observer):
+            if getattr(part, "weights_only", False):   # the group-wise (per-group) classes
+                raise NotImplementedError(f"{type(part).__name__} quantizes weights only: it cannot be the "
+                                          "activation quantizer / observer of a layer")
         if getattr(self.activation_quantizer.quantizer, "self_scaled", False):
             # MX blocks of an activation run along its channels, the axis the next layer's
             # dot product runs along ([N, C, ...]; an [N, C] tensor: its rows)

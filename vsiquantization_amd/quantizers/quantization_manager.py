@@ -16,6 +16,9 @@ MI355X differences (behaviour-preserving):
   the reference's Python lists of floats on first read (one sync).
 * Per-channel observer + per-channel quantizer in observe+quantize mode run as ONE
   fused kernel (observe, f64 qparams and fake quant in one read of ``x``).
+* PerGroupMinMaxObserver + PerGroupUniformQuantizer (group-wise weights, "w4 g128") have one
+  branch of their own (``_quantize_per_group``): the same one-kernel observe+quantize while
+  observing, the fixed group-wise forward in eval; everything else about them is refused.
 """
 from __future__ import annotations
 
@@ -34,8 +37,10 @@ from ..fakequant import (observe_parts, observe_tensor, part_slot_doubles,
                          stats_from_row_sums)
 from ..observers.minmax import MinMaxObserver
 from ..observers.per_channel import PerChannelMinMaxObserver
+from ..observers.per_group import PerGroupMinMaxObserver
 from ..utils.registry import CLASS_REGISTRY
 from .per_channel import PerChannelUniformQuantizer
+from .per_group import PerGroupUniformQuantizer
 
 _STAT_NAMES = ("mean_abs_x", "mean_x", "std")
 
@@ -286,6 +291,16 @@ class QuantizationManager(nn.Module):
         (qm.py:55-71)."""
         if self.is_learning_scale or not self.is_observer_qparam:
             return
+        if self._per_group():   # group-wise weights: the observe-only form of their own kernel
+            obs, _ = self._per_group_check()
+            if act is not None:
+                self._per_group_check("activations (they quantize weights only)")
+            self._join()
+            if isinstance(x, torch.Tensor):
+                self._x_device = x.device
+            obs.observe(x)
+            self.scale, self.zero_point = obs.get_scale_zero_point()
+            return
         if act is not None:
             act = self._silu_act(act)
         if isinstance(x, torch.Tensor):
@@ -440,6 +455,8 @@ class QuantizationManager(nn.Module):
             if self.is_quantize:
                 return self.quantizer.quantize(x, self.scale, self.zero_point, self.is_learning_scale)
             return x
+        if self._per_group():
+            return self._quantize_per_group(x, act)
         if act is not None:
             act = self._silu_act(act)
         if self.is_quantize or self.is_learning_scale:
@@ -486,6 +503,55 @@ class QuantizationManager(nn.Module):
                 return self.quantizer.quantize(x, self.scale, self.zero_point, self.is_learning_scale)
             return self.quantizer.quantize(x, self.scale, self.zero_point, self.is_learning_scale,
                                            act=act)
+        return x
+
+    # ------------------------------------------------------------------ group-wise weights
+    def _per_group(self) -> bool:
+        """A PerGroupMinMaxObserver and / or a PerGroupUniformQuantizer is in place."""
+        return isinstance(self.observer, PerGroupMinMaxObserver) or isinstance(self.quantizer,
+                                                                                PerGroupUniformQuantizer)
+
+    def _per_group_check(self, what=None):
+        """The pair this manager's group-wise branch serves, or the refusal that names the class."""
+        obs, q = self.observer, self.quantizer
+        if not (isinstance(obs, PerGroupMinMaxObserver) and isinstance(q, PerGroupUniformQuantizer)):
+            raise NotImplementedError(f"{type(obs).__name__} with {type(q).__name__}: group-wise quantization needs "
+                                      "PerGroupMinMaxObserver together with PerGroupUniformQuantizer")
+        if what is not None:
+            raise NotImplementedError(f"{type(q).__name__} / {type(obs).__name__} do not support {what}")
+        if self.dist_group is not None:
+            raise NotImplementedError(f"{type(obs).__name__} does not support a multi-GPU dist_group: group-wise "
+                                      "weights are observed on one GPU")
+        # dist_defer (calibrate_qat_model's default) is for per-tensor observers: a group-wise
+        # manager observes per call under it, as the per-channel observers do
+        if obs.group_size != q.group_size:   # the quantizer's is the one users set
+            obs.group_size = q.group_size
+        return obs, q
+
+    def _quantize_per_group(self, x, act):
+        """quantize() for PerGroupMinMaxObserver + PerGroupUniformQuantizer: observing (training with
+        observed qparams, calibration) is one observe + qparams + fake-quant kernel, or the
+        observe-only form of it when not quantizing; eval (is_observer_qparam False) is the fixed
+        group-wise forward with the qparams kept.  No stats records: mean_abs_x / mean_x / std
+        feed the learnable-scale init, which group-wise quantization does not have."""
+        obs, q = self._per_group_check()
+        if act is not None:
+            self._per_group_check("activations (they quantize weights only)")
+        if self.is_learning_scale:
+            self._per_group_check("learnable qparams (is_learning_scale): set is_learning_scale = False")
+        self._join()
+        if isinstance(x, torch.Tensor):
+            self._x_device = x.device
+        if self.is_observer_qparam:
+            if self.is_quantize:
+                y = obs.observe_quantize(x, q)
+                self.scale, self.zero_point = obs.get_scale_zero_point()
+                return y
+            obs.observe(x)
+            self.scale, self.zero_point = obs.get_scale_zero_point()
+            return x
+        if self.is_quantize:
+            return q.quantize(x, self.scale, self.zero_point, False)
         return x
 
     def export_packed(self, x):
@@ -642,6 +708,8 @@ class QuantizationManager(nn.Module):
         does not read its scale back to the host on every call (and stays graph-capturable)."""
         if getattr(self.quantizer, "self_scaled", False):
             return   # block scales come from the data: nothing to learn
+        if self._per_group():
+            self._per_group_check("make_learn_qparameter (there are no learnable group scales)")
         self._join()
         dev = self._home_device()
         s = self.scale
