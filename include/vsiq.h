@@ -459,6 +459,29 @@ int vsiq_pg_fq_fwd_f32(const float *x, float *y, void *codes, uint64_t *mask, in
                        void *stream);
 int vsiq_pg_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t rows, int64_t rowlen,
                         int64_t group, const double *scale, void *stream);
+/*
+ * Learnable (LSQ) group qparams: the backward of vsiq_pg_fq_fwd_f32 (zp_round = zp_learn)
+ * with the gradients of the [rows, ngr] scale and zero point, in the layout above.
+ * Group (r, j) is processed exactly as vsiq_host_lsq_bwd_f32 (act none) processes a tensor
+ * holding that group's elements alone, with scale[r, j] and zp[r, j]:
+ *   gx                   = (mask ? g*s : 0) / s                                   (fp32)
+ *   grad_scale_out[r, j] = gscale * sum [ g*(q - zp) - (mask ? g*s : 0) * ((x/s)/s) ]
+ *   grad_zp_out[r, j]    = gscale * sum [ (mask ? g*s : 0) - g*s ] * (rint(zp[r, j]) in [qmin, qmax])
+ * with s = fp32(scale[r, j]); zp_learn == 1: the zero point is clamp(rint(zp[r, j])), the
+ * forward's zp_round, and grad_zp_out is written; zp_learn == 0: zp as given and grad_zp_out,
+ * when not NULL, written 0.  Any other zp_learn is VSIQ_E_ARG (mode 2 is not offered for
+ * groups).  zp is required, grad_zp_out nullable; other argument errors as
+ * vsiq_pg_fq_fwd_f32; rows == 0 returns 0.
+ * The terms are K4's fp32 terms and the sums f64: each lane adds its up to 4 elements'
+ * terms, then the group's G/4 lanes are folded in a fixed tree inside their wave.  The
+ * order is a function of (rowlen, group) only, so results are the same bits run to run;
+ * there are no floating-point atomics, and one group's sum never enters another's.
+ * One launch; no allocation, synchronisation, workspace or counters: capturable into a
+ * HIP graph.
+ */
+int vsiq_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen, int64_t group,
+                        const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,
+                        double *grad_scale_out, double *grad_zp_out, void *stream);
 
 /*
  * Learnable (LSQ) backward (K4): grad_x plus the scale / zero-point gradients.
@@ -1003,6 +1026,10 @@ int vsiq_host_pg_fq_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t row
                             const double *scale, const double *zp, int zp_round, int qmin, int qmax);
 int vsiq_host_pg_ste_bwd_f32(const float *g, const uint8_t *mask, float *gx, int64_t rows, int64_t rowlen,
                              int64_t group, const double *scale);
+/* vsiq_pg_lsq_bwd_f32 on the host: vsiq_host_lsq_bwd_f32 (act none) group by group */
+int vsiq_host_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen, int64_t group,
+                             const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,
+                             double *grad_scale_out, double *grad_zp_out);
 /* Per-channel along axis 1 ([N, C, ...] activations, LSQFakeQuantize's broadcast of
  * [1, C, 1, ...] parameters, quantizers/lsq_module.py:141-143) on the host, in the device
  * ABI's vsiq_pcm_* layout: rows = N * channels rows of rowlen elements, row r in channel

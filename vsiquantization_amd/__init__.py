@@ -10,6 +10,7 @@ Importing the package registers the quantizer/observer classes by name in
   PercentileObserver, MSEObserver                   (calibrators that clip the min / max range)
   PerChannelMSEObserver                             (MSEObserver's search on every out-channel row)
   PerGroupUniformQuantizer, PerGroupMinMaxObserver  (group-wise weights, groups of 32..256: "w4 g128")
+  PerGroupLSQQuantizer                              (the same with learnable [rows, groups] qparams: LSQ)
   MXQuantizer                                       (OCP MX block scaling: MXFP4 / MXFP6 / MXFP8)
 
 plus ``LSQFakeQuantize`` (quantizers/lsq_module.py, the torch.ao-based LSQ module).
@@ -32,7 +33,7 @@ from .observers.percentile import PercentileObserver  # noqa: F401
 from .observers.mse import MSEObserver  # noqa: F401
 from .observers.per_channel_mse import PerChannelMSEObserver  # noqa: F401
 from .observers.per_group import PerGroupMinMaxObserver  # noqa: F401
-from .quantizers.per_group import PerGroupUniformQuantizer  # noqa: F401
+from .quantizers.per_group import PerGroupLSQQuantizer, PerGroupUniformQuantizer  # noqa: F401
 from .quantizers.quantization_manager import QuantizationManager  # noqa: F401
 from .quantizers.fake_quantize import FakeQuantize  # noqa: F401
 from .quantizers.lsq_module import LSQFakeQuantize  # noqa: F401
@@ -45,6 +46,7 @@ from .quantizers.adaround import AdaRoundWeight  # noqa: F401
 from .utils.adaround import adaround_layer, adaround_model  # noqa: F401
 from .fakequant import mx_dequant, mx_fake_quant  # noqa: F401
 from .fakequant import per_group_fake_quant, per_group_observe_fq, pg_ste_backward  # noqa: F401
+from .fakequant import PerGroupLearnFn, pg_lsq_backward  # noqa: F401
 from .quantizers.mx import MXQuantizer  # noqa: F401
 from .utils.quantize_manager import (disable_model_launches, enable_model_launches,  # noqa: F401
                                      model_launches_enabled)

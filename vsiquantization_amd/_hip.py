@@ -262,6 +262,10 @@ _SIGS = {
                                      c_int], c_int),
     "vsiq_host_pg_fq_fwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int], c_int),
     "vsiq_host_pg_ste_bwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p], c_int),
+    "vsiq_pg_lsq_bwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int, c_d, c_p, c_p, c_p],
+                            c_int),
+    "vsiq_host_pg_lsq_bwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_int, c_int, c_int, c_d, c_p, c_p],
+                                 c_int),
     "vsiq_host_threads": ([], c_int),
     "vsiq_host_simd": ([], c_int),
     "vsiq_act_fwd_f32": ([c_p, c_p, c_i64, c_int, c_p], c_int),

@@ -733,6 +733,31 @@ int vsiq_host_pg_ste_bwd_f32(const float *g, const uint8_t *mask, float *gx, int
   return rc.load();
 }
 
+// learnable group qparams: every group the per-tensor learnable backward on the group's
+// elements alone with (scale, zp)[r, j] -- its gx, its t * gscale and its zero-point gradient
+int vsiq_host_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen, int64_t group,
+                             const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,
+                             double *grad_scale_out, double *grad_zp_out) {
+  if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || qmin > qmax || zp_learn < 0 || zp_learn > 1)
+    return VSIQ_E_ARG;
+  if (rows == 0) return 0;
+  if (!g || !x || !gx || !scale || !zp || !grad_scale_out) return VSIQ_E_ARG;
+  const int64_t ngr = pg_groups_per_row(rowlen, group);
+  std::atomic<int> rc{0};
+  Pool::get().run(rows, [&](int64_t r) {
+    for (int64_t j = 0; j < ngr; ++j) {
+      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group), q = r * ngr + j;
+      double out[2] = {0.0, 0.0};
+      const int e = vsiq_host_lsq_bwd_f32(g + o, x + o, gx + o, len, kActNone, scale[q], zp[q], zp_learn, qmin, qmax,
+                                          gscale, out);
+      if (e) rc.store(e);
+      grad_scale_out[q] = out[0];
+      if (grad_zp_out) grad_zp_out[q] = out[1];
+    }
+  });
+  return rc.load();
+}
+
 // Axis 1 ([N, C, ...]): row r = n * channels + c in channel c, each row the per-tensor host
 // call with its channel's qparams; the learnable gradients summed per channel over its
 // rows in row order (f64), then times gscale once -- for channels == rows exactly the

@@ -1,6 +1,7 @@
 // k_pg.hip — group-wise (per-group) weight quantization: observe + qparams + fake quant in
 // one launch (vsiq_pg_observe_fq_f32), the forward with given [rows, ngr] qparams
-// (vsiq_pg_fq_fwd_f32) and the STE backward (vsiq_pg_ste_bwd_f32).  Layout: k_pg.cuh.
+// (vsiq_pg_fq_fwd_f32), the STE backward (vsiq_pg_ste_bwd_f32) and the learnable (LSQ)
+// backward with per-group scale / zero-point gradients (vsiq_pg_lsq_bwd_f32).  Layout: k_pg.cuh.
 //
 // Lane mapping (all three kernels).  A wave takes one 256-element chunk of one row: lane l
 // of the wave on chunk c of row r owns elements 256c + 4l .. 256c + 4l + 3 of that row, the
@@ -21,6 +22,7 @@
 // takes at the tuning knob's default; the scalar path (rowlen % 4 != 0 or unaligned
 // pointers: per-element accesses of the same lanes) uses plain ones, as K3's does.  This
 // file does not read the knob.
+#include "k_body.cuh"
 #include "k_pg.cuh"
 #include "vsiq_common.cuh"
 
@@ -72,21 +74,32 @@ __device__ __forceinline__ PGTask pg_task(const PGView &v, int u) {
   return k;
 }
 
-// min / max over the `gl` adjacent lanes of a group, returned to each of them.  Whole wave
-// active (every call site is wave-uniform); gl is kernel-uniform.
-template <typename Op>
-__device__ __forceinline__ float pg_reduce(float v, uint32_t gl, Op op) {
-  const float id = Op::identity();
+// min / max (fp32) or sum (f64: every DPP step and lane read on both 32-bit halves) over the
+// `gl` adjacent lanes of a group, returned to each of them, in a fixed tree.  Whole wave
+// active (every call site is wave-uniform); gl is kernel-uniform.  No step reads a lane of
+// another group, so one group's value never enters another's result.
+template <typename T>
+__device__ __forceinline__ T pg_readlane(T v, int lane) {
+  if constexpr (sizeof(T) == 4) {
+    return __builtin_bit_cast(T, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
+  } else {
+    const uint64_t u = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
+    return __builtin_bit_cast(T, ((uint64_t)hi << 32) | lo);
+  }
+}
+
+template <typename T, typename Op>
+__device__ __forceinline__ T pg_reduce(T v, uint32_t gl, Op op) {
+  const T id = Op::identity();
   v = op(v, dpp<0xB1>(v, id));    // quad_perm [1,0,3,2]
   v = op(v, dpp<0x4E>(v, id));    // quad_perm [2,3,0,1]
   v = op(v, dpp<0x141>(v, id));   // row_half_mirror -> every lane: its 8 lanes'
   if (gl >= 16) v = op(v, dpp<0x140>(v, id));   // row_mirror -> its 16-lane row's
   if (gl >= 32) {
-    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-    const float a = op(r0, r1), b = op(r2, r3);
+    const T r0 = pg_readlane(v, 0), r1 = pg_readlane(v, 16), r2 = pg_readlane(v, 32), r3 = pg_readlane(v, 48);
+    const T a = op(r0, r1), b = op(r2, r3);
     v = gl == 64 ? op(a, b) : (threadIdx.x % kWave < 32 ? a : b);
   }
   return v;
@@ -258,9 +271,57 @@ __global__ __launch_bounds__(kBlock) void k_pg_ste_bwd(const float *__restrict__
 }
 
 // ----------------------------------------------------------------------------
+// learnable (LSQ) backward: gx and the [rows, ngr] f64 scale / zero-point gradients
+// ----------------------------------------------------------------------------
+// Every 4-element group runs K4's element code (k_body.cuh lsq_group_out, act none) with its
+// quantization group's qparams.  lsq_group_out adds +0 for an element past the row's end --
+// a lane past it (its clamped loads are copies of the row's last elements) or the tail of a
+// partial 4-element group on the scalar path -- so such elements leave both sums unchanged.
+// Each lane's up to 4 terms are summed in f64, the group's gl lanes folded by pg_reduce, and
+// the group's first lane writes sum * gscale: no LDS, no workspace, no atomics, one launch.
+template <bool VEC, int U, bool ZPL>
+__global__ __launch_bounds__(kBlock) void k_pg_lsq_bwd(const float *__restrict__ g, const float *__restrict__ x,
+                                                       float *__restrict__ gx, PGView v, PGFixed a, double gscale,
+                                                       double *__restrict__ gs_out, double *__restrict__ gz_out) {
+  PGTask k[U];
+  f4 xv[U], gv[U];
+  double sc[U], zc[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    k[u] = pg_task<U>(v, u);
+    xv[u] = load_group_c<VEC, VEC>(x + k[u].row * v.rowlen, k[u].i, k[u].ng, v.rowlen);
+    gv[u] = load_group_c<VEC, VEC>(g + k[u].row * v.rowlen, k[u].i, k[u].ng, v.rowlen);
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    sc[u] = a.scale[k[u].qi];
+    zc[u] = a.zp[k[u].qi];
+  }
+  const uint32_t lane = threadIdx.x % kWave;
+  const uint32_t seg = lane & ~(v.gl - 1);
+  f4 o[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const QPSrc s{nullptr, nullptr, nullptr, sc[u], zc[u], a.lo, a.hi, ZPL, 0};
+    const QP p = load_qp(s);   // ZPL: the forward's clamp(rint(zp))
+    LsqAcc c{0.0, 0.0};
+    o[u] = lsq_group_out<ZPL, kActNone>(k[u].i, k[u].ng, v.rowlen, xv[u], gv[u], p, c);
+    c.t = pg_reduce(c.t, v.gl, AddD());
+    if (ZPL) c.z = pg_reduce(c.z, v.gl, AddD());
+    if (k[u].live && k[u].qvalid && lane == seg) {
+      gs_out[k[u].qi] = c.t * gscale;
+      if (gz_out) gz_out[k[u].qi] = ZPL ? lsq_grad_zp(c.z, s, p, gscale) : 0.0;
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    if (k[u].live && k[u].i < k[u].ng) store_group<VEC, VEC>(gx + k[u].row * v.rowlen, k[u].i, v.rowlen, o[u]);
+}
+
+// ----------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------
-constexpr int kPgU = 4;   // tasks per wave where the grid still fills the device (else 1)
+constexpr int kPgU = 4;  // tasks per wave where the grid still fills the device (else 1)
 
 // rc 0 and the view, or an argument error (rows > 0 here)
 static int pg_view(int64_t rows, int64_t rowlen, int64_t group, PGView *v) {
@@ -299,6 +360,14 @@ static void launch_pg_fixed(const float *x, float *y, uint8_t *c, uint64_t *m, c
   else if (c) hipLaunchKernelGGL((k_pg_fq_fwd<VEC, U, true, false>), grid, block, 0, st, x, y, c, m, v, a);
   else if (m) hipLaunchKernelGGL((k_pg_fq_fwd<VEC, U, false, true>), grid, block, 0, st, x, y, c, m, v, a);
   else hipLaunchKernelGGL((k_pg_fq_fwd<VEC, U, false, false>), grid, block, 0, st, x, y, c, m, v, a);
+}
+
+template <bool VEC, int U>
+static void launch_pg_lsq(const float *g, const float *x, float *gx, const PGView &v, const PGFixed &a, double gscale,
+                          double *gs, double *gz, hipStream_t st) {
+  const dim3 grid = pg_grid(v, U), block(kBlock);
+  if (a.zp_round) hipLaunchKernelGGL((k_pg_lsq_bwd<VEC, U, true>), grid, block, 0, st, g, x, gx, v, a, gscale, gs, gz);
+  else hipLaunchKernelGGL((k_pg_lsq_bwd<VEC, U, false>), grid, block, 0, st, g, x, gx, v, a, gscale, gs, gz);
 }
 
 }  // namespace vsiq
@@ -361,6 +430,24 @@ int vsiq_pg_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t
   else if (pg_per_wave(v) == kPgU)
     hipLaunchKernelGGL((k_pg_ste_bwd<true, kPgU>), pg_grid(v, kPgU), block, 0, st, g, mask, gx, v, scale);
   else hipLaunchKernelGGL((k_pg_ste_bwd<true, 1>), pg_grid(v, 1), block, 0, st, g, mask, gx, v, scale);
+  return launch_rc();
+}
+
+int vsiq_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen, int64_t group,
+                        const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,
+                        double *grad_scale_out, double *grad_zp_out, void *stream) {
+  if (rows < 0 || rowlen <= 0 || qmin > qmax || !pg_group_ok(group) || zp_learn < 0 || zp_learn > 1)
+    return VSIQ_E_ARG;
+  if (rows == 0) return 0;
+  if (!g || !x || !gx || !scale || !zp || !grad_scale_out) return VSIQ_E_ARG;
+  PGView v;
+  if (pg_view(rows, rowlen, group, &v)) return VSIQ_E_ARG;
+  const PGFixed a{scale, zp, zp_learn, (float)qmin, (float)qmax};
+  const bool vec = (rowlen % 4 == 0) && aligned16(g) && aligned16(x) && aligned16(gx);
+  hipStream_t st = (hipStream_t)stream;
+  if (!vec) launch_pg_lsq<false, 1>(g, x, gx, v, a, gscale, grad_scale_out, grad_zp_out, st);
+  else if (pg_per_wave(v) == kPgU) launch_pg_lsq<true, kPgU>(g, x, gx, v, a, gscale, grad_scale_out, grad_zp_out, st);
+  else launch_pg_lsq<true, 1>(g, x, gx, v, a, gscale, grad_scale_out, grad_zp_out, st);
   return launch_rc();
 }
 

@@ -1194,6 +1194,60 @@ class PerGroupFQFn(torch.autograd.Function):
         return pg_ste_backward(gy, mask, scale, ctx.group), None, None, None, None, None
 
 
+def pg_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, group_size):
+    """The group-wise learnable (LSQ) backward, one launch (csrc/k_pg.hip): (grad_x, grad_scale
+    f64 [rows, ngr], grad_zp f64 [rows, ngr]).  Every group is the per-tensor learnable backward
+    on its elements alone with (scale, zp)[row, group]; ``learn_zp``: the forward used
+    clamp(rint(zp)) (per_group_fake_quant's zp_round) and grad_zp is its gradient, else zeros.
+    The gradients are already multiplied by ``gscale``.  A CPU g: the host loops."""
+    group = check_group_size(group_size)
+    g, host = _pg_input(g, "grad_output")
+    x, xhost = _pg_input(x)
+    if xhost != host or x.device != g.device:
+        raise ValueError(f"grad_output is on {g.device}, x on {x.device}")
+    if x.shape != g.shape:
+        raise ValueError(f"grad_output has shape {tuple(g.shape)}, x {tuple(x.shape)}")
+    rows, rowlen, ngr = _pg_view(g, group)
+    s = _pg_f64(scale, rows, ngr, g.device, "scale")
+    z = _pg_f64(zp, rows, ngr, g.device, "zero point")
+    if host:
+        return _host.pg_lsq_backward(g, x, s, z, group, qmin, qmax, gscale, learn_zp)
+    gx = torch.empty_like(g)
+    gs = torch.empty_like(s)
+    gz = torch.empty_like(s)
+    rc = H.lib().vsiq_pg_lsq_bwd_f32(H.ptr(g), H.ptr(x), H.ptr(gx), _i64(rows), _i64(rowlen), _i64(group),
+                                     H.ptr(s), H.ptr(z), int(bool(learn_zp)), int(qmin), int(qmax), float(gscale),
+                                     H.ptr(gs), H.ptr(gz), H.stream_of(g.device))
+    H.check(rc, "vsiq_pg_lsq_bwd_f32")
+    return gx, gs, gz
+
+
+class PerGroupLearnFn(torch.autograd.Function):
+    """Learnable group-wise fake quant: per_group_fake_quant forward (zp_round = learn_zp),
+    pg_lsq_backward backward.  scale / zero_point are tensors of rows * ngr entries (any shape,
+    any float dtype); their gradients come back in that shape / dtype, already multiplied by
+    ``gscale`` (ScaleGradient, uniform.py:242-255)."""
+
+    @staticmethod
+    def forward(ctx, x, scale, zero_point, qmin, qmax, gscale, learn_zp, group_size):
+        y, _, _ = per_group_fake_quant(x, scale, zero_point, qmin, qmax, group_size=group_size,
+                                       zp_round=learn_zp)   # checks x
+        ctx.save_for_backward(x.contiguous())
+        ctx.scale, ctx.zp = scale, zero_point
+        ctx.args = (qmin, qmax, gscale, learn_zp, group_size)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (x,) = ctx.saved_tensors
+        qmin, qmax, gscale, learn_zp, group_size = ctx.args
+        s, z = ctx.scale, ctx.zp
+        gx, gs, gz = pg_lsq_backward(gy.contiguous(), x, s, z, qmin, qmax, gscale, learn_zp, group_size)
+        gs = _qparam_grad(gs, s, ctx.needs_input_grad[1])
+        gz = _qparam_grad(gz, z, learn_zp and ctx.needs_input_grad[2])
+        return gx, gs, gz, None, None, None, None, None
+
+
 # --------------------------------------------------------------------------- export
 PACK_BITS = (2, 4, 8)
 

@@ -312,6 +312,23 @@ def pg_ste_backward(g, mask, scale, group):
     return gx
 
 
+def pg_lsq_backward(g, x, scale, zp, group, qmin, qmax, gscale, learn_zp):
+    """Host counterpart of fakequant.pg_lsq_backward (``scale`` / ``zp`` f64 [rows, ngr] on the
+    CPU): each group the per-tensor learnable host loop on its elements alone; (grad_x,
+    grad_scale f64 [rows, ngr], grad_zp f64 [rows, ngr])."""
+    g = _f32(g, "grad_output")
+    x = _f32(x)
+    rows, rowlen = _rows(g)
+    gx = torch.empty_like(g)
+    gs = torch.empty_like(scale)
+    gz = torch.empty_like(scale)
+    rc = H.lib().vsiq_host_pg_lsq_bwd_f32(H.ptr(g), H.ptr(x), H.ptr(gx), _i64(rows), _i64(rowlen), _i64(group),
+                                          H.ptr(scale), H.ptr(zp), int(bool(learn_zp)), int(qmin), int(qmax),
+                                          float(gscale), H.ptr(gs), H.ptr(gz))
+    H.check(rc, "vsiq_host_pg_lsq_bwd_f32")
+    return gx, gs, gz
+
+
 def pc_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, axis=0):
     """Host counterpart of fakequant.pc_lsq_backward (``axis`` 0: [C, ...] weights, 1:
     [N, C, ...] activations -- LSQFakeQuantize): each row the per-tensor learnable host

@@ -9,7 +9,7 @@ with groups restarting at every row (the last group of a row may be short) and o
 csrc/k_pg.hip; scale and zero point come back as float64 [rows, groups] device tensors (no host
 sync).  CPU tensors take the native host loops group by group: the same bits.
 
-Weights only, fp32 only, fixed (observed) qparams only; it is deliberately NOT a
+Weights only, fp32 only (PerGroupLSQQuantizer learns the qparams observed here); it is deliberately NOT a
 PerChannelMinMaxObserver, so none of the per-channel kernels' branches take it.
 """
 from __future__ import annotations

@@ -5,15 +5,19 @@ out-channel row: "w4 g128".  ``quantize(x, scale, zero_point, False)`` takes the
 host loops).  ``group_size`` defaults to 128 and is set on the instance, the way
 MXQuantizer.elem_format is; QuantizationManager keeps the observer's in step.
 
-Weights only, fp32 only, fixed qparams only (no learnable group scales, no packed export, no
-AdaRound yet).  It is deliberately NOT a UniformQuantizer / PerChannelUniformQuantizer, so none of
-the per-tensor or per-channel kernels' branches take it.
+Weights only, fp32 only, no packed export, no AdaRound yet.  It is deliberately NOT a
+UniformQuantizer / PerChannelUniformQuantizer, so none of the per-tensor or per-channel kernels'
+branches take it.
+
+PerGroupUniformQuantizer itself has fixed (observed) qparams only and refuses
+``is_learning_scale``.  Learnable group scales (LSQ) come under a name of their own,
+PerGroupLSQQuantizer below, the way LSQQuantizer sits beside UniformQuantizer.
 """
 from __future__ import annotations
 
 import torch
 
-from ..fakequant import PerGroupFQFn, check_group_size, per_group_fake_quant
+from ..fakequant import PerGroupFQFn, PerGroupLearnFn, _pg_view, check_group_size, per_group_fake_quant
 from ..utils.registry import register_class
 from .base import BaseQuantizer
 
@@ -61,3 +65,45 @@ class PerGroupUniformQuantizer(BaseQuantizer):
     def __repr__(self):
         return (f"{type(self).__name__}(num_bits={self.num_bits}, symmetric={self.symmetric}, "
                 f"qmin={self.qmin}, qmax={self.qmax}, group_size={self._group_size})")
+
+
+@register_class
+class PerGroupLSQQuantizer(PerGroupUniformQuantizer):
+    """PerGroupUniformQuantizer whose [rows, groups] scale -- and, asymmetric, zero point -- can
+    be learned (LSQ): ``quantize(x, scale, zero_point, True)`` runs the group-wise forward with
+    the zero point rounded and clamped when it is learned, and one backward launch
+    (fakequant.pg_lsq_backward) that returns grad_x and every group's scale / zero-point gradient.
+    Used with PerGroupMinMaxObserver, whose observed qparams QuantizationManager.
+    make_learn_qparameter turns into Parameters.
+
+    The gradient scale is (qmax * group_size) ** -0.5: group_size is the nominal element count
+    per scale, the analogue of PerChannelUniformQuantizer's numel / C.  It is one number for the
+    whole tensor, so it also applies to a row's short last group, which holds fewer elements.
+
+    Under torch.no_grad(), or when neither x nor a qparam requires grad, the same forward runs
+    without the autograd Function (a frozen x with a scale Parameter still trains the scale).
+    ``is_learning_scale`` False behaves as the base class; ``act`` still raises."""
+
+    def __init__(self, num_bits=8, symmetric=True, group_size=128):
+        super().__init__(num_bits, symmetric, group_size)
+        self.learns_zero_point = not symmetric
+
+    def quantize(self, x, scale, zero_point, is_learning_scale=False, act=None):
+        if not is_learning_scale or act is not None:
+            return super().quantize(x, scale, zero_point, False, act=act)
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
+            what = x.dtype if isinstance(x, torch.Tensor) else type(x).__name__
+            raise TypeError(f"PerGroupLSQQuantizer: only float32 tensors are supported, got {what}")
+        if not isinstance(scale, torch.Tensor):
+            raise RuntimeError("PerGroupLSQQuantizer.quantize needs a [rows, groups] scale (observe with "
+                               "PerGroupMinMaxObserver, then QuantizationManager.make_learn_qparameter)")
+        G = self._group_size
+        if not isinstance(zero_point, torch.Tensor):   # the manager's 0 for a symmetric quantizer
+            rows, _, ngr = _pg_view(x, G)
+            zero_point = torch.full((rows, ngr), float(zero_point), dtype=torch.float64, device=x.device)
+        learn_zp = self.learns_zero_point
+        if not (x.requires_grad or scale.requires_grad or zero_point.requires_grad) or not torch.is_grad_enabled():
+            return per_group_fake_quant(x, scale, zero_point, self.qmin, self.qmax, group_size=G,
+                                        zp_round=learn_zp)[0]
+        gscale = float((self.qmax * G) ** -0.5)
+        return PerGroupLearnFn.apply(x, scale, zero_point, self.qmin, self.qmax, gscale, learn_zp, G)

@@ -19,6 +19,8 @@ MI355X differences (behaviour-preserving):
 * PerGroupMinMaxObserver + PerGroupUniformQuantizer (group-wise weights, "w4 g128") have one
   branch of their own (``_quantize_per_group``): the same one-kernel observe+quantize while
   observing, the fixed group-wise forward in eval; everything else about them is refused.
+  PerGroupLSQQuantizer in the quantizer's place adds learnable [rows, groups] qparams
+  (``is_learning_scale`` / ``make_learn_qparameter``); packed export and AdaRound stay refused.
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ from ..observers.per_channel import PerChannelMinMaxObserver
 from ..observers.per_group import PerGroupMinMaxObserver
 from ..utils.registry import CLASS_REGISTRY
 from .per_channel import PerChannelUniformQuantizer
-from .per_group import PerGroupUniformQuantizer
+from .per_group import PerGroupLSQQuantizer, PerGroupUniformQuantizer
 
 _STAT_NAMES = ("mean_abs_x", "mean_x", "std")
 
@@ -538,7 +540,12 @@ class QuantizationManager(nn.Module):
         if act is not None:
             self._per_group_check("activations (they quantize weights only)")
         if self.is_learning_scale:
-            self._per_group_check("learnable qparams (is_learning_scale): set is_learning_scale = False")
+            if not isinstance(q, PerGroupLSQQuantizer):
+                self._per_group_check("learnable qparams (is_learning_scale): set is_learning_scale = False, "
+                                      "or use PerGroupLSQQuantizer")
+            # learned group qparams: no observer call, no stats record (collect_qparameter's rule)
+            self._join()
+            return q.quantize(x, self.scale, self.zero_point, True) if self.is_quantize else x
         self._join()
         if isinstance(x, torch.Tensor):
             self._x_device = x.device
@@ -709,7 +716,7 @@ class QuantizationManager(nn.Module):
         if getattr(self.quantizer, "self_scaled", False):
             return   # block scales come from the data: nothing to learn
         if self._per_group():
-            self._per_group_check("make_learn_qparameter (there are no learnable group scales)")
+            return self._make_learn_group_qparameter()
         self._join()
         dev = self._home_device()
         s = self.scale
@@ -734,9 +741,30 @@ class QuantizationManager(nn.Module):
         else:
             self.zero_point = 0
 
+    def _make_learn_group_qparameter(self):
+        """make_learn_qparameter for group-wise weights: the observed [rows, groups] f64 scale --
+        and, asymmetric, zero point (+ 1e-9 as above) -- as Parameters on the observer's device;
+        PerGroupLSQQuantizer only."""
+        obs, q = self._per_group_check()
+        if not isinstance(q, PerGroupLSQQuantizer):
+            self._per_group_check("make_learn_qparameter (learnable group scales: use PerGroupLSQQuantizer)")
+        self._join()
+        s = self.scale
+        if not isinstance(s, torch.Tensor):
+            raise RuntimeError(f"{type(q).__name__}.make_learn_qparameter: nothing observed yet -- the [rows, groups] "
+                               f"scale comes from {type(obs).__name__} (calibrate first)")
+        dev = obs.run_min.device if isinstance(obs.run_min, torch.Tensor) else s.device
+        self.scale = nn.Parameter(s.detach().to(dev, torch.float64).clone(), requires_grad=True)
+        if q.learns_zero_point:
+            z = self.zero_point.detach().to(dev, torch.float64).clone()
+            self.zero_point = nn.Parameter(z + 1e-9, requires_grad=True)
+        else:
+            self.zero_point = 0
+
     def init_scaling_factor_for_learning(self):
-        """scale = 2 * mean(mean_abs_x) / sqrt(2^(b-1) - 1)  (qm.py:105-112)."""
-        if getattr(self.quantizer, "self_scaled", False):
+        """scale = 2 * mean(mean_abs_x) / sqrt(2^(b-1) - 1)  (qm.py:105-112).  A group-wise
+        manager records no mean|x|: its observed [rows, groups] qparams stay in place."""
+        if getattr(self.quantizer, "self_scaled", False) or self._per_group():
             return
         self.scale = 2 * np.mean(self.mean_abs_x) / np.sqrt(2 ** (self.bits_width - 1) - 1)
 
