@@ -482,6 +482,36 @@ int vsiq_pg_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t
 int vsiq_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen, int64_t group,
                         const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,
                         double *grad_scale_out, double *grad_zp_out, void *stream);
+/*
+ * The per-group MSE observer (PerGroupMSEObserver; csrc/k_pg_mse.hip; added within ABI 13:
+ * purely additive): the error-minimising clip search on every group of the layout above, in ONE
+ * launch and one read of the tensor.  Group (r, j) is processed exactly as
+ * vsiq_pc_observe_mse_f32 processes a row holding that group's elements alone:
+ *   mn, mx and the NaN flag are the group's own (NaN-ignoring fp32 min / max, "the group holds
+ *   a NaN"); lo_k = (float)((double)mn * r[k]), hi_k = (float)((double)mx * r[k]); validity,
+ *   E_k (the f64 sum of the squared errors of the element function's output on the grid
+ *   (qmin, qmax)), the strict-< pick from k = 0, the running update of (run_min, run_max)[r, j]
+ *   with (lo_k*, hi_k*) and the f64 qparams of the updated state follow that definition.
+ * Fallback is per group: group (r, j) is vsiq_pg_observe_fq_f32's ((lo, hi) = (mn, mx), pick 0,
+ * its errors all +inf) when it holds a NaN, mn == mx (a one-element last group included), mn or
+ * mx is not finite, or count == 1; one group's fallback or values never reach another group.
+ * Outputs: run_min / run_max fp32 [rows, ngr] in/out, scale_out / zp_out f64 [rows, ngr],
+ * clip_out f64 [rows, ngr, 2] = (lo, hi), err_out f64 [rows, ngr, count] (NULLABLE: it is the
+ * largest output by far), pick_out int32 [rows, ngr].  With y != NULL, y / codes / mask are
+ * vsiq_pg_fq_fwd_f32's for the qparams this call returns, bit for bit; y == NULL observes only
+ * (codes and mask must then be NULL too); codes and mask are nullable.
+ * The terms are fixed by the definition; the order of a group's f64 sums is the
+ * implementation's, a function of (rowlen, group, count) only: no floating-point atomics, no
+ * workspace, the same bits run to run.  `ratios` is a HOST f64[count] and travels by value with
+ * the launch: capturable into a HIP graph.
+ * VSIQ_E_ARG: as vsiq_pg_observe_fq_f32 (clip_out and pick_out are required too), and count
+ * outside [1, 128], ratios NULL, ratios[0] != 1, a ratio outside (0, 1] or NaN, qmin >= qmax.
+ * rows == 0 returns 0.  fp32 only.
+ */
+int vsiq_pg_observe_mse_f32(const float *x, float *y, void *codes, uint64_t *mask, int64_t rows, int64_t rowlen,
+                            int64_t group, const double *ratios, int count, float *run_min, float *run_max,
+                            double *scale_out, double *zp_out, double *clip_out, double *err_out, int32_t *pick_out,
+                            int symmetric, int qmin, int qmax, double qden, double eps, void *stream);
 
 /*
  * Learnable (LSQ) backward (K4): grad_x plus the scale / zero-point gradients.
@@ -1026,6 +1056,13 @@ int vsiq_host_pg_fq_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t row
                             const double *scale, const double *zp, int zp_round, int qmin, int qmax);
 int vsiq_host_pg_ste_bwd_f32(const float *g, const uint8_t *mask, float *gx, int64_t rows, int64_t rowlen,
                              int64_t group, const double *scale);
+/* vsiq_pg_observe_mse_f32 on the host: vsiq_host_observe_f32, vsiq_host_observe_mse_f32 and
+ * vsiq_host_fq_fwd_f32 on each group alone (mask: one byte per element; no codes; err_out
+ * nullable).  The same argument errors. */
+int vsiq_host_pg_observe_mse_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen, int64_t group,
+                                 const double *ratios, int count, float *run_min, float *run_max, double *scale_out,
+                                 double *zp_out, double *clip_out, double *err_out, int32_t *pick_out, int symmetric,
+                                 int qmin, int qmax, double qden, double eps);
 /* vsiq_pg_lsq_bwd_f32 on the host: vsiq_host_lsq_bwd_f32 (act none) group by group */
 int vsiq_host_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen, int64_t group,
                              const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,

@@ -53,9 +53,14 @@ FLAGS = [
 # k_pc_mse.hip (the per-channel search, the same wave step from k_mse_step.cuh) likewise.
 # k_pack.hip (the export's quantize + pack and unpack + dequantize kernels) runs the forward
 # kernels' element code: default flags, like k_fq.hip and k_pc.hip.
+# k_pg.hip (the group-wise kernels) has default flags; k_pg_mse.hip (the per-group MSE search,
+# picked up by sources() beside it) is built without packed fp32 instructions (v_pk_*_f32): its
+# hot loop is four independent fp32 element chains per lane against one candidate, exactly what
+# the compiler would pair up, and every term has to be the scalar element function's bits.
 _NO_SLP = ["-fno-slp-vectorize"]
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"k_observe.hip": _NO_SLP, "k_observe_half.hip": _NO_SLP, "k_observe_fq.hip": _NO_SLP,
-              "k_lib.hip": _NO_SLP}
+              "k_lib.hip": _NO_SLP, "k_pg_mse.hip": _NO_PK_F32}
 
 
 def hipcc() -> str:

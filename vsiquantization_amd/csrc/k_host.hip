@@ -700,6 +700,46 @@ int vsiq_host_pg_observe_fq_f32(const float *x, float *y, uint8_t *mask, int64_t
   return rc.load();
 }
 
+// PerGroupMSEObserver on CPU tensors (vsiq_pg_observe_mse_f32's definition): every group what
+// vsiq_host_pc_observe_mse_f32 does with a row that holds it -- the group's record, the search on
+// the group's own running state, the fake quant with the qparams just returned.
+int vsiq_host_pg_observe_mse_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen, int64_t group,
+                                 const double *ratios, int count, float *run_min, float *run_max, double *scale_out,
+                                 double *zp_out, double *clip_out, double *err_out, int32_t *pick_out, int symmetric,
+                                 int qmin, int qmax, double qden, double eps) {
+  if (rows < 0 || rowlen <= 0 || qmin >= qmax || !pg_group_ok(group) || !mse_ratios_ok(ratios, count))
+    return VSIQ_E_ARG;
+  if (rows == 0) return 0;   // as the device entry
+  if (!x || !run_min || !run_max || !scale_out || !zp_out || !clip_out || !pick_out || (!y && mask))
+    return VSIQ_E_ARG;
+  const int64_t ngr = pg_groups_per_row(rowlen, group);
+  std::atomic<int> rc{0};
+  Pool::get().run(rows, [&](int64_t r) {
+    for (int64_t j = 0; j < ngr; ++j) {
+      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group), q = r * ngr + j;
+      float st[2] = {run_min[q], run_max[q]};
+      double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN], err[kMseMaxCand];
+      int e = vsiq_host_observe_f32(x + o, len, kActNone, stats, nullptr, nullptr, symmetric, qden, eps);
+      if (!e)
+        e = vsiq_host_observe_mse_f32(x + o, len, kActNone, stats, ratios, count, qmin, qmax, st, qp, clip_out + 2 * q,
+                                      err_out ? err_out + q * count : err, pick_out + q, symmetric, qden, eps);
+      if (e) {
+        rc.store(e);
+        continue;
+      }
+      run_min[q] = st[0];
+      run_max[q] = st[1];
+      scale_out[q] = qp[VSIQ_QP_SCALE];
+      zp_out[q] = qp[VSIQ_QP_ZP];
+      if (y)
+        e = vsiq_host_fq_fwd_f32(x + o, y + o, nullptr, mask ? mask + o : nullptr, len, kActNone, qp, 0.0, 0.0, 0, 0,
+                                 qmin, qmax);
+      if (e) rc.store(e);
+    }
+  });
+  return rc.load();
+}
+
 int vsiq_host_pg_fq_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen, int64_t group,
                             const double *scale, const double *zp, int zp_round, int qmin, int qmax) {
   if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || (rows > 0 && (!x || !y || !scale || !zp)) || qmin > qmax)

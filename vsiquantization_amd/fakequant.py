@@ -12,6 +12,7 @@ eager torch ops in the reference:
   observe_tensor           observers/minmax.py:32-88 + quantization_manager.py:66-68 (K2)
   per_channel_observe_fq   per-channel MinMax + UniformQuantizer (K3)
   per_group_observe_fq     the same on every group of 32..256 consecutive elements of a row (k_pg.hip)
+  per_group_observe_mse    per_group_observe_fq with each group's range shrunk to its least error (k_pg_mse.hip)
   FakeQuantFixedFn         autograd of uniform.py:55,95 with fixed qparams (STE)
   FakeQuantLearnFn         autograd of uniform.py:47-56 (LSQ: ScaleGradient, STE) (K4)
   FakeQuantLearnMultiFn    FakeQuantLearnFn over many tensors in one launch each way
@@ -1192,6 +1193,74 @@ class PerGroupFQFn(torch.autograd.Function):
     def backward(ctx, gy):
         mask, scale = ctx.saved_tensors
         return pg_ste_backward(gy, mask, scale, ctx.group), None, None, None, None, None
+
+
+def per_group_observe_mse(x: torch.Tensor, *, group_size: int, symmetric: bool, qmin: int, qmax: int,
+                          num_bits: int = 8, eps: float = 1e-8, run_min=None, run_max=None, ratios,
+                          quantize: bool = True, want_mask: bool = False, want_codes: bool = False,
+                          want_errors: bool = False):
+    """Group-wise MSE observe + f64 qparams + fake quant in one launch and one read of x
+    (csrc/k_pg_mse.hip): every group of per_group_observe_fq's view searched as
+    per_channel_observe_mse searches a row holding its elements -- its own min / max, its own
+    candidates ratios[k] * (min, max) scored on the grid (qmin, qmax), its own pick and fallback
+    -- then the running update of (run_min, run_max)[row, group] and the group's f64 qparams
+    (include/vsiq.h states the definition).
+
+    quantize=False observes only (y is None).  Returns per_group_observe_fq's dict plus clip
+    f64 [rows, ngr, 2] = (lo, hi), pick int32 [rows, ngr] and err: f64 [rows, ngr, len(ratios)]
+    with want_errors, else None (it is by far the largest output).  fp32 only; a CPU tensor takes
+    the native host loops (host.pg_observe_mse; byte mask, no codes)."""
+    group = check_group_size(group_size)
+    r = check_mse_ratios(ratios)
+    qmin, qmax = int(qmin), int(qmax)
+    if qmin >= qmax:
+        raise ValueError(f"qmin must be below qmax, got ({qmin}, {qmax})")
+    x, host = _pg_input(x)
+    if host:
+        if want_codes:
+            raise NotImplementedError("per_group_observe_mse: integer codes are written by the HIP kernel only; "
+                                      "the host loops have none")
+        return _host.pg_observe_mse(x, group, symmetric=symmetric, qmin=qmin, qmax=qmax, num_bits=num_bits, eps=eps,
+                                    run_min=run_min, run_max=run_max, ratios=r, quantize=quantize,
+                                    want_mask=want_mask, want_errors=want_errors)
+    dev = x.device
+    rows, rowlen, ngr = _pg_view(x, group)
+    run_min, run_max, y, scale, zp = H.pg_observe_buffers(x, rows, ngr, run_min, run_max, quantize)
+    clip = torch.empty(rows, ngr, 2, dtype=torch.float64, device=dev)
+    err = torch.empty(rows, ngr, len(r), dtype=torch.float64, device=dev) if want_errors else None
+    pick = torch.empty(rows, ngr, dtype=torch.int32, device=dev)
+    mask = H.mask_buffer(rows, rowlen, dev) if (want_mask and quantize) else None
+    codes = H.codes_buffer(x.shape, qmin, dev) if (want_codes and quantize) else None
+    table = (H.c_d * len(r))(*r)
+    rc = H.lib().vsiq_pg_observe_mse_f32(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(mask), _i64(rows), _i64(rowlen),
+                                         _i64(group), table, len(r), H.ptr(run_min), H.ptr(run_max), H.ptr(scale),
+                                         H.ptr(zp), H.ptr(clip), H.ptr(err), H.ptr(pick), int(bool(symmetric)), qmin,
+                                         qmax, qden(symmetric, num_bits, eps), float(eps), H.stream_of(dev))
+    H.check(rc, "vsiq_pg_observe_mse_f32")
+    return dict(y=y, scale=scale, zp=zp, run_min=run_min, run_max=run_max, mask=mask, codes=codes, clip=clip, err=err,
+                pick=pick)
+
+
+class PerGroupObserveMSEFn(torch.autograd.Function):
+    """per_group_observe_mse with the STE backward (pg_ste_backward with the scales returned), in
+    the style of PerGroupObserveFQFn.  Returns (y, scale, zp, pick, err); err is an empty tensor
+    unless ``want_errors``."""
+
+    @staticmethod
+    def forward(ctx, x, group_size, symmetric, qmin, qmax, num_bits, eps, run_min, run_max, ratios, want_errors):
+        r = per_group_observe_mse(x, group_size=group_size, symmetric=symmetric, qmin=qmin, qmax=qmax,
+                                  num_bits=num_bits, eps=eps, run_min=run_min, run_max=run_max, ratios=ratios,
+                                  want_mask=True, want_errors=want_errors)
+        ctx.save_for_backward(r["mask"], r["scale"])
+        ctx.group = group_size
+        err = r["err"] if want_errors else r["scale"].new_zeros(0)
+        ctx.mark_non_differentiable(r["scale"], r["zp"], r["pick"], err)
+        return r["y"], r["scale"], r["zp"], r["pick"], err
+
+    @staticmethod
+    def backward(ctx, gy, _gs, _gz, _gp, _ge):
+        mask, scale = ctx.saved_tensors
+        return (pg_ste_backward(gy, mask, scale, ctx.group),) + (None,) * 10
 
 
 def pg_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, group_size):

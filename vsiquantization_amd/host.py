@@ -288,6 +288,30 @@ def pg_observe_fq(x, group, *, symmetric, qmin, qmax, obs_bits=8, eps=1e-8, run_
     return dict(y=y, scale=scale, zp=zp, run_min=run_min, run_max=run_max, mask=mask, codes=None)
 
 
+def pg_observe_mse(x, group, *, symmetric, qmin, qmax, num_bits=8, eps=1e-8, run_min=None, run_max=None, ratios,
+                   quantize=True, want_mask=False, want_errors=False):
+    """Host counterpart of fakequant.per_group_observe_mse (which has checked ``group``, ``ratios``
+    and the grid): the host MSE loop on each group with its own running state, then the host fake
+    quant with the qparams returned.  Same dict as the device function (byte mask, no codes)."""
+    x = _f32(x)
+    rows, rowlen = _rows(x)
+    ngr = -(-rowlen // group)
+    run_min, run_max, y, scale, zp = H.pg_observe_buffers(x, rows, ngr, run_min, run_max, quantize)
+    _check_state(run_min, run_max)
+    mask = torch.empty(x.shape, dtype=torch.uint8) if (want_mask and quantize) else None
+    clip = torch.empty(rows, ngr, 2, dtype=torch.float64)
+    err = torch.empty(rows, ngr, len(ratios), dtype=torch.float64) if want_errors else None
+    pick = torch.empty(rows, ngr, dtype=torch.int32)
+    table = (H.c_d * len(ratios))(*ratios)
+    rc = H.lib().vsiq_host_pg_observe_mse_f32(H.ptr(x), H.ptr(y), H.ptr(mask), _i64(rows), _i64(rowlen), _i64(group),
+                                              table, len(ratios), H.ptr(run_min), H.ptr(run_max), H.ptr(scale),
+                                              H.ptr(zp), H.ptr(clip), H.ptr(err), H.ptr(pick), int(bool(symmetric)),
+                                              int(qmin), int(qmax), qden(symmetric, num_bits, eps), float(eps))
+    H.check(rc, "vsiq_host_pg_observe_mse_f32")
+    return dict(y=y, scale=scale, zp=zp, run_min=run_min, run_max=run_max, mask=mask, codes=None, clip=clip, err=err,
+                pick=pick)
+
+
 def pg_fake_quant(x, scale, zp, group, qmin, qmax, *, zp_round=False, want_mask=False):
     """Group-wise fake quant with given [rows, ngr] f64 CPU qparams on the host: (y, mask | None)."""
     x = _f32(x)

@@ -5,3 +5,4 @@ from .percentile import PercentileObserver  # noqa: F401
 from .mse import MSEObserver  # noqa: F401
 from .per_channel_mse import PerChannelMSEObserver  # noqa: F401
 from .per_group import PerGroupMinMaxObserver  # noqa: F401
+from .per_group_mse import PerGroupMSEObserver  # noqa: F401

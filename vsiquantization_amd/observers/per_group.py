@@ -11,6 +11,9 @@ sync).  CPU tensors take the native host loops group by group: the same bits.
 
 Weights only, fp32 only (PerGroupLSQQuantizer learns the qparams observed here); it is deliberately NOT a
 PerChannelMinMaxObserver, so none of the per-channel kernels' branches take it.
+PerGroupMSEObserver (per_group_mse.py) subclasses it: the same view, state and protocol with every
+group's range shrunk to its least quantization error, and QuantizationManager's group-wise branch
+takes it through the two entry points below (``observe``, ``observe_quantize``).
 """
 from __future__ import annotations
 
