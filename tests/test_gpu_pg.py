@@ -77,7 +77,7 @@ def test_kernels_equal_the_reshaped_k3_route_and_the_host_loops(rows, rowlen, G,
 
 def test_four_tasks_per_wave_from_the_grid_size_threshold_on():
     """From 64 wave tasks (256-element row chunks) per CU on, a wave takes 4 tasks instead of 1
-    (k_pg.hip pg_per_wave): the smallest tensor over that threshold, with a 4-element last chunk
+    (k_pg_wave.cuh pg_per_wave): the smallest tensor over that threshold, with a 4-element last chunk
     per row (rowlen 3076 = 12 * 256 + 4) and a last workgroup that is not full, and the
     largest one still under it."""
     cus = torch.cuda.get_device_properties(0).multi_processor_count

@@ -5,8 +5,9 @@ The launchers of these files pick a kernel instantiation from which outputs are 
 for the learnable backward, whether the zero point is learned), and the entry points pick a launch
 form: the per-element (scalar) path, the vector path with one task per wave, the vector path with
 kPgU tasks per wave (k_pg_mse: scalar / vector only).  This test reads the
-``hipLaunchKernelGGL((k_pg_...<...>)`` sites and the ``launch_pg_...<...>(`` calls, crosses the
-two, and requires TABLE to name, for every instantiation, test functions that run it.  A new arm
+``hipLaunchKernelGGL((k_pg_...<...>)`` sites, the forms ``with_pg_form`` lists (csrc/k_pg_wave.cuh)
+and which launcher or kernel each ``with_pg_form(vec, `` / ``with_bool(vec, `` call reaches, crosses
+them, and requires TABLE to name, for every instantiation, test functions that run it.  A new arm
 or launch form fails it until someone names its tests; a removed arm, or a renamed or removed
 test, fails it too.  No GPU is used and no test module is imported: the sources are read as text
 (template arguments only, never compiled code) and the test modules parsed with ``ast``.
@@ -18,15 +19,17 @@ import re
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vsiquantization_amd", "csrc")
 TESTS = os.path.join(ROOT, "tests")
-FILES = ("k_pg.hip", "k_pg_mse.hip")
+FILES = ("k_pg_wave.cuh", "k_pg.hip", "k_pg_mse.hip")
 
 SITE = re.compile(r"hipLaunchKernelGGL\(\((k_pg_\w+)<([^<>]*)>\)")     # a launch: kernel, template arguments
-CALL = re.compile(r"\b(launch_pg_\w+)<([^<>]*)>\(")                    # an entry point choosing a launch form
+VIA = re.compile(r"\b(with_pg_form|with_bool)\(vec,[^;]*?\b((?:launch|k)_pg_\w+)<")   # a dispatcher, what it reaches
+FORM = re.compile(r"\bf\(BoolC<(\w+)>\{\}, IntC<(\w+)>\{\}\)")             # a form with_pg_form lists
 LAUNCHER = re.compile(r"^static void (launch_pg_\w+)\(", re.M)         # a launcher's definition
 INSTANCE = re.compile(r"\bk_pg_\w+<")                                  # any instantiation at all
+CALL = re.compile(r"\blaunch_pg_\w+<")                                 # any call of a launcher at all
 
 SCALAR, VEC1, VECU, VECTOR = "scalar", "vector, 1 task per wave", "vector, kPgU tasks per wave", "vector"
-FORMS = {("false", "1"): SCALAR, ("true", "1"): VEC1, ("true", "kPgU"): VECU, ("false",): SCALAR, ("true",): VECTOR}
+FORMS = {("false", "1"): SCALAR, ("true", "1"): VEC1, ("true", "kPgU"): VECU}
 
 # the arms by the template arguments behind VEC (and U): <QUANT, CODES, MASK>, <CODES, MASK>, <ZPL>
 OBSERVE = {"false, false, false": "observe only", "true, false, false": "plain", "true, true, false": "codes only",
@@ -78,34 +81,34 @@ def _args(text):
 
 
 def instantiations(text):
-    """{(kernel, arm, launch form)} of one source text.  A site inside a launcher (template
-    arguments VEC, [U,] arm...) ships its arm in every form the entry points call the launcher
-    with; a site that spells its form out (<false, 1>) ships that one."""
+    """{(kernel, arm, launch form)} of the source text.  A site inside a launcher (template
+    arguments VEC, [U,] arm...) ships its arm in every form of the dispatcher whose lambda calls
+    the launcher; a site inside such a lambda (decltype(V)::value, ...) in every form of that one."""
     launchers = [(m.start(), m.group(1)) for m in LAUNCHER.finditer(text)]
-    forms = {}
-    for m in CALL.finditer(text):
-        forms.setdefault(m.group(1), set()).add(FORMS[_args(m.group(2))])
+    listed = {"with_pg_form": {FORMS[m.groups()] for m in FORM.finditer(text)}, "with_bool": {SCALAR, VECTOR}}
+    forms, calls = {}, 0
+    for m in VIA.finditer(text):
+        forms.setdefault(m.group(2), set()).update(listed[m.group(1)])
+        calls += m.group(2).startswith("launch_pg_")
+    assert calls == len(CALL.findall(text)), "a launcher called outside with_pg_form(vec, / with_bool(vec,"
     out, sites = set(), 0
     for m in SITE.finditer(text):
         sites += 1
         kernel, args = m.group(1), _args(m.group(2))
-        if args[0] == "VEC":
-            owner = [name for pos, name in launchers if pos < m.start()][-1]
-            arm = ", ".join(a for a in args[1:] if a != "U")
-            assert forms.get(owner), (owner, "a launcher no entry point calls")
-            out |= {(kernel, ARMS[kernel][arm], f) for f in forms[owner]}
-        else:
-            out.add((kernel, ARMS[kernel][""], FORMS[args]))
+        owner = kernel if args[0] != "VEC" else [name for pos, name in launchers if pos < m.start()][-1]
+        arm = ", ".join(a for a in args if a not in ("VEC", "U") and not a.startswith("decltype("))
+        assert forms.get(owner), (owner, "a launcher or kernel no dispatcher reaches, or a dispatcher with no forms")
+        out |= {(kernel, ARMS[kernel][arm], f) for f in forms[owner]}
     assert sites == len(INSTANCE.findall(text)), "an instantiation that is no hipLaunchKernelGGL((k_pg_...<...>) site"
     return out
 
 
 def _shipped():
-    out = set()
-    for name in FILES:
+    text = ""
+    for name in FILES:   # one text: the forms are listed in the header, the sites in the two .hip files
         with open(os.path.join(CSRC, name)) as f:
-            out |= instantiations(f.read())
-    return out
+            text += f.read()
+    return instantiations(text)
 
 
 def _functions(module):
@@ -117,21 +120,26 @@ def _functions(module):
 
 def test_the_parser_reduces_a_site_to_kernel_arm_and_form():
     text = """
+decltype(auto) with_pg_form(bool vec, const PGView &v, F &&f) {
+  return !vec ? f(BoolC<false>{}, IntC<1>{}) : f(BoolC<true>{}, IntC<kPgU>{});
+}
 static void launch_pg_new(const float *x) {
   if (c) hipLaunchKernelGGL((k_pg_fq_fwd<VEC, U, true, false>), grid, block, 0, st, x);
   else hipLaunchKernelGGL((k_pg_fq_fwd<VEC, U, false, false>), grid, block, 0, st, x);
 }
 int entry() {
-  if (!vec) launch_pg_new<false, 1>(x);
-  else launch_pg_new<true, kPgU>(x);
-  hipLaunchKernelGGL((k_pg_ste_bwd<true, 1>), pg_grid(v, 1), block, 0, st, g);
+  with_pg_form(vec, v, [&](auto V, auto U) { launch_pg_new<decltype(V)::value, decltype(U)::value>(x); });
+  with_bool(vec, [&](auto V) {
+    hipLaunchKernelGGL((k_pg_ste_bwd<decltype(V)::value>), pg_grid(v, 1), block, 0, st, g);
+  });
 }
 """
     assert instantiations(text) == {("k_pg_fq_fwd", "codes only", SCALAR), ("k_pg_fq_fwd", "codes only", VECU),
                                     ("k_pg_fq_fwd", "plain", SCALAR), ("k_pg_fq_fwd", "plain", VECU),
-                                    ("k_pg_ste_bwd", "-", VEC1)}
-    for broken in (text.replace("hipLaunchKernelGGL((k_pg_ste_bwd<true, 1>)", "k_pg_ste_bwd<true, 1><<<1, 2>>>("),
-                   text.replace("true, false>", "true, maybe>"), text.replace("<true, kPgU>(x)", "<true, 2>(x)")):
+                                    ("k_pg_ste_bwd", "-", SCALAR), ("k_pg_ste_bwd", "-", VECTOR)}
+    for broken in (text.replace("hipLaunchKernelGGL((k_pg_ste_bwd<decltype(V)::value>)", "k_pg_ste_bwd<true><<<1, 2>>>("),
+                   text.replace("true, false>", "true, maybe>"), text.replace("IntC<kPgU>", "IntC<2>"),
+                   text.replace("int entry() {", "int entry() {\n  launch_pg_new<true, 8>(x);")):
         try:
             instantiations(broken)
         except (AssertionError, KeyError):

@@ -302,6 +302,20 @@ void short_rows(int64_t rows, int64_t rowlen, F &&row) {
   });
 }
 
+// the group-wise view (k_pg.cuh): rows on the pool, a row's groups in order, each f(o, len, q)
+// with the group's first element, its length and its index in the [rows, ngr] arrays; the
+// last nonzero rc an f returned
+template <class F>
+int pg_groups(int64_t rows, int64_t rowlen, int64_t group, F &&f) {
+  const int64_t ngr = pg_groups_per_row(rowlen, group);
+  std::atomic<int> rc{0};
+  Pool::get().run(rows, [&](int64_t r) {
+    for (int64_t j = 0; j < ngr; ++j)
+      if (const int e = f(r * rowlen + j * group, std::min(group, rowlen - j * group), r * ngr + j)) rc.store(e);
+  });
+  return rc.load();
+}
+
 }  // namespace host
 }  // namespace vsiq
 
@@ -583,6 +597,49 @@ int vsiq_host_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t n, 
 // _fq_fwd_f32 / _ste_bwd_f32 / _lsq_bwd_f32 on that row alone).  Rows go to the pool
 // (a row's own chunk loop then runs serially inside it), or, for fewer than
 // kPoolMinChunks rows, one after the other with the pool inside each row.
+//
+// One segment (a row; below, a group) with its running state and qparams at index q: the
+// per-tensor observe on its elements alone, then, with y, the per-tensor fake quant with the
+// qparams just written.  `stats`: the segment's record.
+static int seg_observe_fq(const float *x, float *y, uint8_t *mask, int64_t len, int64_t q, float *run_min,
+                          float *run_max, double *scale_out, double *zp_out, double *stats, int symmetric, double qden,
+                          double eps, int qmin, int qmax) {
+  float st[2] = {run_min[q], run_max[q]};
+  double qp[VSIQ_QP_LEN];
+  int e = vsiq_host_observe_f32(x, len, kActNone, stats, st, qp, symmetric, qden, eps);
+  run_min[q] = st[0];
+  run_max[q] = st[1];
+  scale_out[q] = qp[VSIQ_QP_SCALE];
+  zp_out[q] = qp[VSIQ_QP_ZP];
+  if (!e && y) e = vsiq_host_fq_fwd_f32(x, y, nullptr, mask, len, kActNone, qp, 0.0, 0.0, 0, 0, qmin, qmax);
+  return e;
+}
+
+// the same for the MSE observers: the segment's record, then the search on its own running state
+static int seg_observe_mse(const float *x, int64_t len, int64_t q, const double *ratios, int count, float *run_min,
+                           float *run_max, double *scale_out, double *zp_out, double *clip_out, double *err_out,
+                           int32_t *pick_out, double *stats, double *qp, int symmetric, int qmin, int qmax,
+                           double qden, double eps) {
+  float st[2] = {run_min[q], run_max[q]};
+  double err[kMseMaxCand];
+  int e = vsiq_host_observe_f32(x, len, kActNone, stats, nullptr, nullptr, symmetric, qden, eps);
+  if (!e)
+    e = vsiq_host_observe_mse_f32(x, len, kActNone, stats, ratios, count, qmin, qmax, st, qp, clip_out + 2 * q,
+                                  err_out ? err_out + q * count : err, pick_out + q, symmetric, qden, eps);
+  if (e) return e;
+  run_min[q] = st[0];
+  run_max[q] = st[1];
+  scale_out[q] = qp[VSIQ_QP_SCALE];
+  zp_out[q] = qp[VSIQ_QP_ZP];
+  return 0;
+}
+
+static void put_row_stats(double *row_stats, int64_t r, const double *stats) {
+  row_stats[3 * r] = stats[VSIQ_ST_SUMABS];
+  row_stats[3 * r + 1] = stats[VSIQ_ST_SUM];
+  row_stats[3 * r + 2] = stats[VSIQ_ST_SUMSQ];
+}
+
 int vsiq_host_pc_observe_fq_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen,
                                 float *run_min, float *run_max, double *scale_out, double *zp_out,
                                 double *row_stats, int symmetric, double qden, double eps, int qmin, int qmax) {
@@ -590,22 +647,11 @@ int vsiq_host_pc_observe_fq_f32(const float *x, float *y, uint8_t *mask, int64_t
     return VSIQ_E_ARG;
   std::atomic<int> rc{0};
   Pool::get().run(rows, [&](int64_t r) {
-    const float *xr = x + r * rowlen;
-    float st[2] = {run_min[r], run_max[r]};
-    double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN];
-    int e = vsiq_host_observe_f32(xr, rowlen, kActNone, stats, st, qp, symmetric, qden, eps);
-    run_min[r] = st[0];
-    run_max[r] = st[1];
-    scale_out[r] = qp[VSIQ_QP_SCALE];
-    zp_out[r] = qp[VSIQ_QP_ZP];
-    if (row_stats) {
-      row_stats[3 * r] = stats[VSIQ_ST_SUMABS];
-      row_stats[3 * r + 1] = stats[VSIQ_ST_SUM];
-      row_stats[3 * r + 2] = stats[VSIQ_ST_SUMSQ];
-    }
-    if (!e && y)
-      e = vsiq_host_fq_fwd_f32(xr, y + r * rowlen, nullptr, mask ? mask + r * rowlen : nullptr, rowlen, kActNone,
-                               qp, 0.0, 0.0, 0, 0, qmin, qmax);
+    const int64_t o = r * rowlen;
+    double stats[VSIQ_ST_LEN];
+    const int e = seg_observe_fq(x + o, y ? y + o : nullptr, mask ? mask + o : nullptr, rowlen, r, run_min, run_max,
+                                 scale_out, zp_out, stats, symmetric, qden, eps, qmin, qmax);
+    if (row_stats) put_row_stats(row_stats, r, stats);
     if (e) rc.store(e);
   });
   return rc.load();
@@ -625,26 +671,11 @@ int vsiq_host_pc_observe_mse_f32(const float *x, float *y, uint8_t *mask, int64_
   if (!mse_ratios_ok(ratios, count) || qmin >= qmax) return VSIQ_E_ARG;
   std::atomic<int> rc{0};
   Pool::get().run(rows, [&](int64_t r) {
-    const float *xr = x + r * rowlen;
-    float st[2] = {run_min[r], run_max[r]};
-    double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN], err[kMseMaxCand];
-    int e = vsiq_host_observe_f32(xr, rowlen, kActNone, stats, nullptr, nullptr, symmetric, qden, eps);
-    if (!e)
-      e = vsiq_host_observe_mse_f32(xr, rowlen, kActNone, stats, ratios, count, qmin, qmax, st, qp, clip_out + 2 * r,
-                                    err_out ? err_out + r * count : err, pick_out + r, symmetric, qden, eps);
-    if (e) {
-      rc.store(e);
-      return;
-    }
-    run_min[r] = st[0];
-    run_max[r] = st[1];
-    scale_out[r] = qp[VSIQ_QP_SCALE];
-    zp_out[r] = qp[VSIQ_QP_ZP];
-    if (row_stats) {
-      row_stats[3 * r] = stats[VSIQ_ST_SUMABS];
-      row_stats[3 * r + 1] = stats[VSIQ_ST_SUM];
-      row_stats[3 * r + 2] = stats[VSIQ_ST_SUMSQ];
-    }
+    double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN];
+    const int e = seg_observe_mse(x + r * rowlen, rowlen, r, ratios, count, run_min, run_max, scale_out, zp_out,
+                                  clip_out, err_out, pick_out, stats, qp, symmetric, qmin, qmax, qden, eps);
+    if (e) rc.store(e);
+    else if (row_stats) put_row_stats(row_stats, r, stats);
   });
   if (rc.load() || !y) return rc.load();
   return vsiq_host_pcm_fq_fwd_f32(x, y, mask, rows, rowlen, rows, scale_out, zp_out, 0, qmin, qmax);
@@ -679,25 +710,11 @@ int vsiq_host_pg_observe_fq_f32(const float *x, float *y, uint8_t *mask, int64_t
   if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || qmin > qmax) return VSIQ_E_ARG;
   if (rows == 0) return 0;   // as the device entry
   if (!x || !run_min || !run_max || !scale_out || !zp_out || (!y && mask)) return VSIQ_E_ARG;
-  const int64_t ngr = pg_groups_per_row(rowlen, group);
-  std::atomic<int> rc{0};
-  Pool::get().run(rows, [&](int64_t r) {
-    for (int64_t j = 0; j < ngr; ++j) {
-      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group), q = r * ngr + j;
-      float st[2] = {run_min[q], run_max[q]};
-      double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN];
-      int e = vsiq_host_observe_f32(x + o, len, kActNone, stats, st, qp, symmetric, qden, eps);
-      run_min[q] = st[0];
-      run_max[q] = st[1];
-      scale_out[q] = qp[VSIQ_QP_SCALE];
-      zp_out[q] = qp[VSIQ_QP_ZP];
-      if (!e && y)
-        e = vsiq_host_fq_fwd_f32(x + o, y + o, nullptr, mask ? mask + o : nullptr, len, kActNone, qp, 0.0, 0.0, 0, 0,
-                                 qmin, qmax);
-      if (e) rc.store(e);
-    }
+  return pg_groups(rows, rowlen, group, [&](int64_t o, int64_t len, int64_t q) {
+    double stats[VSIQ_ST_LEN];
+    return seg_observe_fq(x + o, y ? y + o : nullptr, mask ? mask + o : nullptr, len, q, run_min, run_max, scale_out,
+                          zp_out, stats, symmetric, qden, eps, qmin, qmax);
   });
-  return rc.load();
 }
 
 // PerGroupMSEObserver on CPU tensors (vsiq_pg_observe_mse_f32's definition): every group what
@@ -712,65 +729,34 @@ int vsiq_host_pg_observe_mse_f32(const float *x, float *y, uint8_t *mask, int64_
   if (rows == 0) return 0;   // as the device entry
   if (!x || !run_min || !run_max || !scale_out || !zp_out || !clip_out || !pick_out || (!y && mask))
     return VSIQ_E_ARG;
-  const int64_t ngr = pg_groups_per_row(rowlen, group);
-  std::atomic<int> rc{0};
-  Pool::get().run(rows, [&](int64_t r) {
-    for (int64_t j = 0; j < ngr; ++j) {
-      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group), q = r * ngr + j;
-      float st[2] = {run_min[q], run_max[q]};
-      double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN], err[kMseMaxCand];
-      int e = vsiq_host_observe_f32(x + o, len, kActNone, stats, nullptr, nullptr, symmetric, qden, eps);
-      if (!e)
-        e = vsiq_host_observe_mse_f32(x + o, len, kActNone, stats, ratios, count, qmin, qmax, st, qp, clip_out + 2 * q,
-                                      err_out ? err_out + q * count : err, pick_out + q, symmetric, qden, eps);
-      if (e) {
-        rc.store(e);
-        continue;
-      }
-      run_min[q] = st[0];
-      run_max[q] = st[1];
-      scale_out[q] = qp[VSIQ_QP_SCALE];
-      zp_out[q] = qp[VSIQ_QP_ZP];
-      if (y)
-        e = vsiq_host_fq_fwd_f32(x + o, y + o, nullptr, mask ? mask + o : nullptr, len, kActNone, qp, 0.0, 0.0, 0, 0,
-                                 qmin, qmax);
-      if (e) rc.store(e);
-    }
+  return pg_groups(rows, rowlen, group, [&](int64_t o, int64_t len, int64_t q) {
+    double qp[VSIQ_QP_LEN], stats[VSIQ_ST_LEN];
+    int e = seg_observe_mse(x + o, len, q, ratios, count, run_min, run_max, scale_out, zp_out, clip_out, err_out,
+                            pick_out, stats, qp, symmetric, qmin, qmax, qden, eps);
+    if (!e && y)
+      e = vsiq_host_fq_fwd_f32(x + o, y + o, nullptr, mask ? mask + o : nullptr, len, kActNone, qp, 0.0, 0.0, 0, 0,
+                               qmin, qmax);
+    return e;
   });
-  return rc.load();
 }
 
 int vsiq_host_pg_fq_fwd_f32(const float *x, float *y, uint8_t *mask, int64_t rows, int64_t rowlen, int64_t group,
                             const double *scale, const double *zp, int zp_round, int qmin, int qmax) {
   if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || (rows > 0 && (!x || !y || !scale || !zp)) || qmin > qmax)
     return VSIQ_E_ARG;
-  const int64_t ngr = pg_groups_per_row(rowlen, group);
-  std::atomic<int> rc{0};
-  Pool::get().run(rows, [&](int64_t r) {
-    for (int64_t j = 0; j < ngr; ++j) {
-      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group), q = r * ngr + j;
-      const int e = vsiq_host_fq_fwd_f32(x + o, y + o, nullptr, mask ? mask + o : nullptr, len, kActNone, nullptr,
-                                         scale[q], zp[q], zp_round, 0, qmin, qmax);
-      if (e) rc.store(e);
-    }
+  return pg_groups(rows, rowlen, group, [&](int64_t o, int64_t len, int64_t q) {
+    return vsiq_host_fq_fwd_f32(x + o, y + o, nullptr, mask ? mask + o : nullptr, len, kActNone, nullptr, scale[q],
+                                zp[q], zp_round, 0, qmin, qmax);
   });
-  return rc.load();
 }
 
 int vsiq_host_pg_ste_bwd_f32(const float *g, const uint8_t *mask, float *gx, int64_t rows, int64_t rowlen,
                              int64_t group, const double *scale) {
   if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || (rows > 0 && (!g || !mask || !gx || !scale)))
     return VSIQ_E_ARG;
-  const int64_t ngr = pg_groups_per_row(rowlen, group);
-  std::atomic<int> rc{0};
-  Pool::get().run(rows, [&](int64_t r) {
-    for (int64_t j = 0; j < ngr; ++j) {
-      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group);
-      const int e = vsiq_host_ste_bwd_f32(g + o, mask + o, nullptr, gx + o, len, kActNone, scale[r * ngr + j]);
-      if (e) rc.store(e);
-    }
+  return pg_groups(rows, rowlen, group, [&](int64_t o, int64_t len, int64_t q) {
+    return vsiq_host_ste_bwd_f32(g + o, mask + o, nullptr, gx + o, len, kActNone, scale[q]);
   });
-  return rc.load();
 }
 
 // learnable group qparams: every group the per-tensor learnable backward on the group's
@@ -782,20 +768,14 @@ int vsiq_host_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t 
     return VSIQ_E_ARG;
   if (rows == 0) return 0;
   if (!g || !x || !gx || !scale || !zp || !grad_scale_out) return VSIQ_E_ARG;
-  const int64_t ngr = pg_groups_per_row(rowlen, group);
-  std::atomic<int> rc{0};
-  Pool::get().run(rows, [&](int64_t r) {
-    for (int64_t j = 0; j < ngr; ++j) {
-      const int64_t o = r * rowlen + j * group, len = std::min(group, rowlen - j * group), q = r * ngr + j;
-      double out[2] = {0.0, 0.0};
-      const int e = vsiq_host_lsq_bwd_f32(g + o, x + o, gx + o, len, kActNone, scale[q], zp[q], zp_learn, qmin, qmax,
-                                          gscale, out);
-      if (e) rc.store(e);
-      grad_scale_out[q] = out[0];
-      if (grad_zp_out) grad_zp_out[q] = out[1];
-    }
+  return pg_groups(rows, rowlen, group, [&](int64_t o, int64_t len, int64_t q) {
+    double out[2] = {0.0, 0.0};
+    const int e = vsiq_host_lsq_bwd_f32(g + o, x + o, gx + o, len, kActNone, scale[q], zp[q], zp_learn, qmin, qmax,
+                                        gscale, out);
+    grad_scale_out[q] = out[0];
+    if (grad_zp_out) grad_zp_out[q] = out[1];
+    return e;
   });
-  return rc.load();
 }
 
 // Axis 1 ([N, C, ...]): row r = n * channels + c in channel c, each row the per-tensor host

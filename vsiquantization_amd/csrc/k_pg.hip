@@ -22,7 +22,7 @@
 // takes at the tuning knob's default; the scalar path (rowlen % 4 != 0 or unaligned
 // pointers: per-element accesses of the same lanes) uses plain ones, as K3's does.  This
 // file does not read the knob.
-#include "k_pg_wave.cuh"   // the lane mapping's code: PGView, pg_task, pg_reduce, pg_quantize, pg_store
+#include "k_pg_wave.cuh"   // the lane mapping's code, the entry checks and the launch forms
 
 namespace vsiq {
 
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void k_pg_observe_fq(const float *__restric
 #pragma unroll
   for (int u = 0; u < U; ++u) {   // all loads of the workgroup's tasks in flight before the first reduction
     k[u] = pg_task<U>(v, u);
-    w[u] = load_group_c<VEC, VEC>(x + k[u].row * v.rowlen, k[u].i, k[u].ng, v.rowlen);
+    w[u] = pg_load<VEC>(x, k[u], v);
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -66,17 +66,11 @@ __global__ __launch_bounds__(kBlock) void k_pg_observe_fq(const float *__restric
   PGOut go[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const f4 e = w[u];   // lanes past the row end replicate members of the row's last group
-    float mn = fminf(fminf(e.x, e.y), fminf(e.z, e.w));
-    float mx = fmaxf(fmaxf(e.x, e.y), fmaxf(e.z, e.w));
-    const bool nanl = (e.x != e.x) | (e.y != e.y) | (e.z != e.z) | (e.w != e.w);
-    mn = pg_reduce(mn, v.gl, MinOp());
-    mx = pg_reduce(mx, v.gl, MaxOp());
-    const bool nan = ((__ballot(nanl) >> seg) & segmask) != 0;
+    const PGRange r = pg_range<false>(w[u], v, seg, segmask);
     float lo = rmn[u], hi = rmx[u];
-    if (!nan) {   // minmax.py:44-47, strict compares; a NaN group changes nothing
-      if (mn < lo) lo = mn;
-      if (mx > hi) hi = mx;
+    if (!r.nan) {   // minmax.py:44-47, strict compares; a NaN group changes nothing (r.mn, r.mx unread)
+      if (r.mn < lo) lo = r.mn;
+      if (r.mx > hi) hi = r.mx;
     }
     double s, z;
     minmax_qparams((double)lo, (double)hi, a.sym, a.qden, a.eps, &s, &z);
@@ -88,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void k_pg_observe_fq(const float *__restric
     }
     if (QUANT) {
       const QP p = make_qp((float)s, (float)z, a.lo, a.hi, 0);
-      go[u] = pg_quantize<VEC, CODES, MASK>(e, p, k[u], v);
+      go[u] = pg_quantize<VEC, CODES, MASK>(w[u], p, k[u], v);
     }
   }
   if (QUANT) {
@@ -109,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_pg_fq_fwd(const float *__restrict__ 
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     k[u] = pg_task<U>(v, u);
-    w[u] = load_group_c<VEC, VEC>(x + k[u].row * v.rowlen, k[u].i, k[u].ng, v.rowlen);
+    w[u] = pg_load<VEC>(x, k[u], v);
   }
   PGOut go[U];
 #pragma unroll
@@ -137,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void k_pg_ste_bwd(const float *__restrict__
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     k[u] = pg_task<U>(v, u);
-    w[u] = load_group_c<VEC, VEC>(g + k[u].row * v.rowlen, k[u].i, k[u].ng, v.rowlen);
+    w[u] = pg_load<VEC>(g, k[u], v);
     const uint64_t *mr = mask + k[u].row * mask_words_per_row(v.rowlen) + 4 * (int64_t)k[u].chunk;   // wave-uniform
 #pragma unroll
     for (int j = 0; j < 4; ++j) m[u][j] = mr[j];
@@ -162,8 +156,7 @@ __global__ __launch_bounds__(kBlock) void k_pg_ste_bwd(const float *__restrict__
     }
   }
 #pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (k[u].live && k[u].i < k[u].ng) store_group<VEC, VEC>(gx + k[u].row * v.rowlen, k[u].i, v.rowlen, o[u]);
+  for (int u = 0; u < U; ++u) pg_store_row<VEC>(k[u], v, gx, o[u]);
 }
 
 // ----------------------------------------------------------------------------
@@ -185,8 +178,8 @@ __global__ __launch_bounds__(kBlock) void k_pg_lsq_bwd(const float *__restrict__
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     k[u] = pg_task<U>(v, u);
-    xv[u] = load_group_c<VEC, VEC>(x + k[u].row * v.rowlen, k[u].i, k[u].ng, v.rowlen);
-    gv[u] = load_group_c<VEC, VEC>(g + k[u].row * v.rowlen, k[u].i, k[u].ng, v.rowlen);
+    xv[u] = pg_load<VEC>(x, k[u], v);
+    gv[u] = pg_load<VEC>(g, k[u], v);
   }
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -210,20 +203,12 @@ __global__ __launch_bounds__(kBlock) void k_pg_lsq_bwd(const float *__restrict__
     }
   }
 #pragma unroll
-  for (int u = 0; u < U; ++u)
-    if (k[u].live && k[u].i < k[u].ng) store_group<VEC, VEC>(gx + k[u].row * v.rowlen, k[u].i, v.rowlen, o[u]);
+  for (int u = 0; u < U; ++u) pg_store_row<VEC>(k[u], v, gx, o[u]);
 }
 
 // ----------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------
-constexpr int kPgU = 4;  // tasks per wave where the grid still fills the device (else 1)
-
-// tasks per wave (the grid of workgroups of kWaves * U tasks: pg_grid)
-static int pg_per_wave(const PGView &v) {
-  return (int64_t)v.tasks >= (int64_t)kWaves * kPgU * 4 * device_cus() ? kPgU : 1;
-}
-
 template <bool VEC, int U>
 static void launch_pg_observe(const float *x, float *y, uint8_t *c, uint64_t *m, const PGView &v, const PGObs &a,
                               hipStream_t st) {
@@ -262,75 +247,60 @@ extern "C" {
 int vsiq_pg_observe_fq_f32(const float *x, float *y, void *codes, uint64_t *mask, int64_t rows, int64_t rowlen,
                            int64_t group, float *run_min, float *run_max, double *scale_out, double *zp_out,
                            int symmetric, int qmin, int qmax, double qden, double eps, void *stream) {
-  if (rows < 0 || rowlen <= 0 || qmin > qmax || !pg_group_ok(group)) return VSIQ_E_ARG;
-  if (rows == 0) return 0;
-  if (!x || !run_min || !run_max || !scale_out || !zp_out) return VSIQ_E_ARG;
-  if (!y && (codes || mask)) return VSIQ_E_ARG;
   PGView v;
-  if (pg_view(rows, rowlen, group, &v)) return VSIQ_E_ARG;
-  if (mask && !aligned8(mask)) return VSIQ_E_ALIGN;
+  int rc;
+  if (!pg_enter(rows, rowlen, group, qmin <= qmax,
+                x && run_min && run_max && scale_out && zp_out && (y || (!codes && !mask)), mask, &v, &rc))
+    return rc;
   const PGObs a{run_min, run_max, scale_out, zp_out, symmetric, (float)qmin, (float)qmax, qden, eps};
   const bool vec = (rowlen % 4 == 0) && aligned16(x) && (!y || aligned16(y)) && (!codes || aligned4(codes));
-  hipStream_t st = (hipStream_t)stream;
-  uint8_t *c = (uint8_t *)codes;
-  if (!vec) launch_pg_observe<false, 1>(x, y, c, mask, v, a, st);
-  else if (pg_per_wave(v) == kPgU) launch_pg_observe<true, kPgU>(x, y, c, mask, v, a, st);
-  else launch_pg_observe<true, 1>(x, y, c, mask, v, a, st);
+  with_pg_form(vec, v, [&](auto V, auto U) {
+    launch_pg_observe<decltype(V)::value, decltype(U)::value>(x, y, (uint8_t *)codes, mask, v, a, (hipStream_t)stream);
+  });
   return launch_rc();
 }
 
 int vsiq_pg_fq_fwd_f32(const float *x, float *y, void *codes, uint64_t *mask, int64_t rows, int64_t rowlen,
                        int64_t group, const double *scale, const double *zp, int zp_round, int qmin, int qmax,
                        void *stream) {
-  if (rows < 0 || rowlen <= 0 || qmin > qmax || !pg_group_ok(group)) return VSIQ_E_ARG;
-  if (rows == 0) return 0;
-  if (!x || !y || !scale || !zp) return VSIQ_E_ARG;
   PGView v;
-  if (pg_view(rows, rowlen, group, &v)) return VSIQ_E_ARG;
-  if (mask && !aligned8(mask)) return VSIQ_E_ALIGN;
+  int rc;
+  if (!pg_enter(rows, rowlen, group, qmin <= qmax, x && y && scale && zp, mask, &v, &rc)) return rc;
   const PGFixed a{scale, zp, zp_round, (float)qmin, (float)qmax};
   const bool vec = (rowlen % 4 == 0) && aligned16(x) && aligned16(y) && (!codes || aligned4(codes));
-  hipStream_t st = (hipStream_t)stream;
-  uint8_t *c = (uint8_t *)codes;
-  if (!vec) launch_pg_fixed<false, 1>(x, y, c, mask, v, a, st);
-  else if (pg_per_wave(v) == kPgU) launch_pg_fixed<true, kPgU>(x, y, c, mask, v, a, st);
-  else launch_pg_fixed<true, 1>(x, y, c, mask, v, a, st);
+  with_pg_form(vec, v, [&](auto V, auto U) {
+    launch_pg_fixed<decltype(V)::value, decltype(U)::value>(x, y, (uint8_t *)codes, mask, v, a, (hipStream_t)stream);
+  });
   return launch_rc();
 }
 
 int vsiq_pg_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t rows, int64_t rowlen,
                         int64_t group, const double *scale, void *stream) {
-  if (rows < 0 || rowlen <= 0 || !pg_group_ok(group)) return VSIQ_E_ARG;
-  if (rows == 0) return 0;
-  if (!g || !mask || !gx || !scale) return VSIQ_E_ARG;
   PGView v;
-  if (pg_view(rows, rowlen, group, &v)) return VSIQ_E_ARG;
-  if (!aligned8(mask)) return VSIQ_E_ALIGN;
+  int rc;
+  if (!pg_enter(rows, rowlen, group, true, g && mask && gx && scale, mask, &v, &rc)) return rc;
   const bool vec = (rowlen % 4 == 0) && aligned16(g) && aligned16(gx);
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 block(kBlock);
-  if (!vec) hipLaunchKernelGGL((k_pg_ste_bwd<false, 1>), pg_grid(v, 1), block, 0, st, g, mask, gx, v, scale);
-  else if (pg_per_wave(v) == kPgU)
-    hipLaunchKernelGGL((k_pg_ste_bwd<true, kPgU>), pg_grid(v, kPgU), block, 0, st, g, mask, gx, v, scale);
-  else hipLaunchKernelGGL((k_pg_ste_bwd<true, 1>), pg_grid(v, 1), block, 0, st, g, mask, gx, v, scale);
+  with_pg_form(vec, v, [&](auto V, auto U) {
+    hipLaunchKernelGGL((k_pg_ste_bwd<decltype(V)::value, decltype(U)::value>), pg_grid(v, decltype(U)::value),
+                       dim3(kBlock), 0, (hipStream_t)stream, g, mask, gx, v, scale);
+  });
   return launch_rc();
 }
 
 int vsiq_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen, int64_t group,
                         const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,
                         double *grad_scale_out, double *grad_zp_out, void *stream) {
-  if (rows < 0 || rowlen <= 0 || qmin > qmax || !pg_group_ok(group) || zp_learn < 0 || zp_learn > 1)
-    return VSIQ_E_ARG;
-  if (rows == 0) return 0;
-  if (!g || !x || !gx || !scale || !zp || !grad_scale_out) return VSIQ_E_ARG;
   PGView v;
-  if (pg_view(rows, rowlen, group, &v)) return VSIQ_E_ARG;
+  int rc;
+  if (!pg_enter(rows, rowlen, group, qmin <= qmax && zp_learn >= 0 && zp_learn <= 1,
+                g && x && gx && scale && zp && grad_scale_out, nullptr, &v, &rc))   // no mask
+    return rc;
   const PGFixed a{scale, zp, zp_learn, (float)qmin, (float)qmax};
   const bool vec = (rowlen % 4 == 0) && aligned16(g) && aligned16(x) && aligned16(gx);
-  hipStream_t st = (hipStream_t)stream;
-  if (!vec) launch_pg_lsq<false, 1>(g, x, gx, v, a, gscale, grad_scale_out, grad_zp_out, st);
-  else if (pg_per_wave(v) == kPgU) launch_pg_lsq<true, kPgU>(g, x, gx, v, a, gscale, grad_scale_out, grad_zp_out, st);
-  else launch_pg_lsq<true, 1>(g, x, gx, v, a, gscale, grad_scale_out, grad_zp_out, st);
+  with_pg_form(vec, v, [&](auto V, auto U) {
+    launch_pg_lsq<decltype(V)::value, decltype(U)::value>(g, x, gx, v, a, gscale, grad_scale_out, grad_zp_out,
+                                                          (hipStream_t)stream);
+  });
   return launch_rc();
 }
 

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void k_pg_mse(const float *__restrict__ x, 
                                                    PGView v, MseRatios R, PgMseArgs a) {
   __shared__ f4 s_c[kWaves][kPgMseGroups * kPgMseStride];
   const PGTask k = pg_task<1>(v, 0);
-  const f4 e = load_group_c<VEC, VEC>(x + k.row * v.rowlen, k.i, k.ng, v.rowlen);
+  const f4 e = pg_load<VEC>(x, k, v);
   float st[2] = {a.run_min[k.qi], a.run_max[k.qi]};
   const uint32_t lane = threadIdx.x % kWave;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave));
@@ -153,13 +153,9 @@ __global__ __launch_bounds__(kBlock) void k_pg_mse(const float *__restrict__ x, 
   const bool writer = k.live && k.qvalid;
 
   // the group's own min / max / NaN flag, as k_pc_mse.hip reduces a row (an all-NaN group: inf, -inf)
-  float mn = fminf(__builtin_inff(), fminf(fminf(e.x, e.y), fminf(e.z, e.w)));
-  float mx = fmaxf(-__builtin_inff(), fmaxf(fmaxf(e.x, e.y), fmaxf(e.z, e.w)));
-  const bool nanl = (e.x != e.x) | (e.y != e.y) | (e.z != e.z) | (e.w != e.w);
-  mn = pg_reduce(mn, v.gl, MinOp());
-  mx = pg_reduce(mx, v.gl, MaxOp());
-  const bool nan = ((__ballot(nanl) >> seg) & segmask) != 0;
-  const bool fb = mse_fallback(mn, mx, nan, a.count);   // the group's own
+  const PGRange r = pg_range<true>(e, v, seg, segmask);
+  const float mn = r.mn, mx = r.mx;
+  const bool nan = r.nan, fb = mse_fallback(mn, mx, nan, a.count);   // the group's own
 
   int pick = 0;
   if (__ballot(!fb) != 0) {   // wave-uniform: some group of the wave searches
@@ -256,22 +252,20 @@ int vsiq_pg_observe_mse_f32(const float *x, float *y, void *codes, uint64_t *mas
                             int64_t group, const double *ratios, int count, float *run_min, float *run_max,
                             double *scale_out, double *zp_out, double *clip_out, double *err_out, int32_t *pick_out,
                             int symmetric, int qmin, int qmax, double qden, double eps, void *stream) {
-  if (rows < 0 || rowlen <= 0 || qmin >= qmax || !pg_group_ok(group) || !mse_ratios_ok(ratios, count))
-    return VSIQ_E_ARG;
-  if (rows == 0) return 0;
-  if (!x || !run_min || !run_max || !scale_out || !zp_out || !clip_out || !pick_out) return VSIQ_E_ARG;
-  if (!y && (codes || mask)) return VSIQ_E_ARG;
   PGView v;
-  if (pg_view(rows, rowlen, group, &v)) return VSIQ_E_ARG;
-  if (mask && !aligned8(mask)) return VSIQ_E_ALIGN;
+  int rc;
+  if (!pg_enter(rows, rowlen, group, qmin < qmax && mse_ratios_ok(ratios, count),
+                x && run_min && run_max && scale_out && zp_out && clip_out && pick_out && (y || (!codes && !mask)),
+                mask, &v, &rc))
+    return rc;
   MseRatios R{};
   for (int k = 0; k < count; ++k) R.r[k] = ratios[k];
   const PgMseArgs a{count,    run_min,   run_max,     scale_out,   zp_out, clip_out, err_out,
                     pick_out, symmetric, (float)qmin, (float)qmax, qden,   eps};
   const bool vec = (rowlen % 4 == 0) && aligned16(x) && (!y || aligned16(y)) && (!codes || aligned4(codes));
-  hipStream_t st = (hipStream_t)stream;
-  if (vec) launch_pg_mse<true>(x, y, (uint8_t *)codes, mask, v, R, a, st);
-  else launch_pg_mse<false>(x, y, (uint8_t *)codes, mask, v, R, a, st);
+  with_bool(vec, [&](auto V) {
+    launch_pg_mse<decltype(V)::value>(x, y, (uint8_t *)codes, mask, v, R, a, (hipStream_t)stream);
+  });
   return launch_rc();
 }
 
