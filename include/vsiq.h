@@ -512,6 +512,55 @@ int vsiq_pg_observe_mse_f32(const float *x, float *y, void *codes, uint64_t *mas
                             int64_t group, const double *ratios, int count, float *run_min, float *run_max,
                             double *scale_out, double *zp_out, double *clip_out, double *err_out, int32_t *pick_out,
                             int symmetric, int qmin, int qmax, double qden, double eps, void *stream);
+/*
+ * Hadamard-rotated group-wise quantization (RotatedPerGroupQuantizer; csrc/k_rot.hip; added
+ * within ABI 13: purely additive).  Every group is rotated by the orthonormal Hadamard matrix
+ * before it is quantized and rotated back after: y = Q(w H) H, so an outlier is spread over its
+ * group instead of setting the group's scale.
+ *
+ * Layout: the group-wise layout above with ONE more restriction, rowlen % G == 0 (a Hadamard
+ * block has no short form); every entry below returns VSIQ_E_ARG otherwise.
+ *
+ * hadamard_G(v) of a group v[0..G) is the in-order radix-2 fast Walsh-Hadamard transform with
+ * the Sylvester matrix in natural order, H[i][j] = (-1)^popcount(i & j):
+ *   for h = 1, 2, 4, ..., G/2: every pair (a, b) = (v[i], v[i + h]) with bit h of i clear
+ *   becomes (a + b, a - b), each ONE fp32 add or subtract, never contracted, denormals kept;
+ *   then every element is multiplied once by c_G = (float)(1.0 / sqrt((double)G))
+ *   (exactly 1/8 for G = 64 and 1/16 for G = 256, one rounding for 32 and 128); a result that
+ *   is a NaN is the canonical quiet NaN 0x7FC00000 (IEEE 754 leaves open which of two different
+ *   NaNs an addition returns; no other result depends on that choice).
+ * Every output is a fixed expression tree of single fp32 operations, so an implementation that
+ * keeps the stage order returns the same bits whether a stage runs inside a lane's registers,
+ * across lanes or in a host loop.  hadamard_G is symmetric and orthonormal; applied twice it
+ * returns v up to rounding (about 2e-7 relative), not bit for bit: the definitions below apply
+ * it again, they never invert it.
+ *
+ * vsiq_pg_hadamard_f32: y = hadamard_G of every group; y == x is allowed.
+ * vsiq_pg_rot_observe_fq_f32: with r = hadamard(x), everything vsiq_pg_observe_fq_f32 defines is
+ * computed on r -- the running update, the f64 qparams, q = the fake-quantized r, the codes and
+ * the 1-bit mask -- then y = hadamard(q).  yr (nullable) receives q, the rotated-domain weight
+ * a deployment stores; the codes belong to it.  y == NULL observes only (yr, codes and mask must
+ * then be NULL); codes and mask are nullable.
+ * vsiq_pg_rot_fq_fwd_f32: the same with given [rows, ngr] qparams, as vsiq_pg_fq_fwd_f32.
+ * vsiq_pg_rot_ste_bwd_f32: gx = hadamard(ste(hadamard(g))) with ste vsiq_pg_ste_bwd_f32's
+ * formula: the exact adjoint of the forward under the straight-through rule.
+ * Each fused call equals, bit for bit in every output, the composition vsiq_pg_hadamard_f32 ->
+ * the group-wise entry it names -> vsiq_pg_hadamard_f32.
+ * All return VSIQ_E_ARG for a bad size, a bad group, a missing pointer or rowlen % G != 0;
+ * rows == 0 returns 0.  One launch each; no workspace, atomics, allocation or synchronisation:
+ * capturable into a HIP graph.  16-byte aligned tensors (codes: 4-byte) take the vector path,
+ * any other alignment a per-element path with the same results.  fp32 only.
+ */
+int vsiq_pg_hadamard_f32(const float *x, float *y, int64_t rows, int64_t rowlen, int64_t group, void *stream);
+int vsiq_pg_rot_observe_fq_f32(const float *x, float *y, float *yr, void *codes, uint64_t *mask, int64_t rows,
+                               int64_t rowlen, int64_t group, float *run_min, float *run_max, double *scale_out,
+                               double *zp_out, int symmetric, int qmin, int qmax, double qden, double eps,
+                               void *stream);
+int vsiq_pg_rot_fq_fwd_f32(const float *x, float *y, float *yr, void *codes, uint64_t *mask, int64_t rows,
+                           int64_t rowlen, int64_t group, const double *scale, const double *zp, int zp_round,
+                           int qmin, int qmax, void *stream);
+int vsiq_pg_rot_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t rows, int64_t rowlen,
+                            int64_t group, const double *scale, void *stream);
 
 /*
  * Learnable (LSQ) backward (K4): grad_x plus the scale / zero-point gradients.
@@ -1067,6 +1116,10 @@ int vsiq_host_pg_observe_mse_f32(const float *x, float *y, uint8_t *mask, int64_
 int vsiq_host_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t rows, int64_t rowlen, int64_t group,
                              const double *scale, const double *zp, int zp_learn, int qmin, int qmax, double gscale,
                              double *grad_scale_out, double *grad_zp_out);
+/* vsiq_pg_hadamard_f32 on the host: hadamard_G's definition as plain loops (y == x allowed;
+ * rowlen % group != 0: VSIQ_E_ARG).  The rotated forwards and backward on CPU tensors are this
+ * call around the vsiq_host_pg_* calls above. */
+int vsiq_host_pg_hadamard_f32(const float *x, float *y, int64_t rows, int64_t rowlen, int64_t group);
 /* Per-channel along axis 1 ([N, C, ...] activations, LSQFakeQuantize's broadcast of
  * [1, C, 1, ...] parameters, quantizers/lsq_module.py:141-143) on the host, in the device
  * ABI's vsiq_pcm_* layout: rows = N * channels rows of rowlen elements, row r in channel

@@ -12,6 +12,7 @@ Importing the package registers the quantizer/observer classes by name in
   PerGroupUniformQuantizer, PerGroupMinMaxObserver  (group-wise weights, groups of 32..256: "w4 g128")
   PerGroupLSQQuantizer                              (the same with learnable [rows, groups] qparams: LSQ)
   PerGroupMSEObserver                               (PerGroupMinMaxObserver with each group's range shrunk to its least error)
+  RotatedPerGroupQuantizer                          (PerGroupUniformQuantizer on Hadamard-rotated groups: y = Q(w H) H)
   MXQuantizer                                       (OCP MX block scaling: MXFP4 / MXFP6 / MXFP8)
 
 plus ``LSQFakeQuantize`` (quantizers/lsq_module.py, the torch.ao-based LSQ module).
@@ -36,6 +37,7 @@ from .observers.per_channel_mse import PerChannelMSEObserver  # noqa: F401
 from .observers.per_group import PerGroupMinMaxObserver  # noqa: F401
 from .observers.per_group_mse import PerGroupMSEObserver  # noqa: F401
 from .quantizers.per_group import PerGroupLSQQuantizer, PerGroupUniformQuantizer  # noqa: F401
+from .quantizers.per_group import RotatedPerGroupQuantizer  # noqa: F401
 from .quantizers.quantization_manager import QuantizationManager  # noqa: F401
 from .quantizers.fake_quantize import FakeQuantize  # noqa: F401
 from .quantizers.lsq_module import LSQFakeQuantize  # noqa: F401
@@ -50,6 +52,8 @@ from .fakequant import mx_dequant, mx_fake_quant  # noqa: F401
 from .fakequant import per_group_fake_quant, per_group_observe_fq, pg_ste_backward  # noqa: F401
 from .fakequant import PerGroupLearnFn, pg_lsq_backward  # noqa: F401
 from .fakequant import per_group_observe_mse  # noqa: F401
+from .fakequant import hadamard_transform, per_group_rot_fake_quant, per_group_rot_observe_fq  # noqa: F401
+from .fakequant import pg_rot_ste_backward  # noqa: F401
 from .quantizers.mx import MXQuantizer  # noqa: F401
 from .utils.quantize_manager import (disable_model_launches, enable_model_launches,  # noqa: F401
                                      model_launches_enabled)

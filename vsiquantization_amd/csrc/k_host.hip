@@ -778,6 +778,32 @@ int vsiq_host_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t 
   });
 }
 
+// hadamard_G (include/vsiq.h) of every group as the definition's loops: stage h pairs i and
+// i + h in place, one fp32 add and one subtract per pair (this file is built uncontracted),
+// then one multiply by c_G.  A group is read whole before it is written, so y == x is fine.
+int vsiq_host_pg_hadamard_f32(const float *x, float *y, int64_t rows, int64_t rowlen, int64_t group) {
+  if (rows < 0 || rowlen <= 0 || !pg_group_ok(group) || rowlen % group) return VSIQ_E_ARG;
+  if (rows == 0) return 0;
+  if (!x || !y) return VSIQ_E_ARG;
+  const float c = (float)(1.0 / std::sqrt((double)group));
+  return pg_groups(rows, rowlen, group, [&](int64_t o, int64_t len, int64_t) {
+    float v[256];
+    for (int64_t i = 0; i < len; ++i) v[i] = x[o + i];
+    for (int64_t h = 1; h < len; h *= 2)
+      for (int64_t i = 0; i < len; ++i)
+        if (!(i & h)) {
+          const float a = v[i], b = v[i + h];
+          v[i] = a + b;
+          v[i + h] = a - b;
+        }
+    for (int64_t i = 0; i < len; ++i) {
+      const float r = v[i] * c;
+      y[o + i] = r != r ? __builtin_nanf("") : r;   // the canonical quiet NaN
+    }
+    return 0;
+  });
+}
+
 // Axis 1 ([N, C, ...]): row r = n * channels + c in channel c, each row the per-tensor host
 // call with its channel's qparams; the learnable gradients summed per channel over its
 // rows in row order (f64), then times gscale once -- for channels == rows exactly the

@@ -13,6 +13,7 @@ eager torch ops in the reference:
   per_channel_observe_fq   per-channel MinMax + UniformQuantizer (K3)
   per_group_observe_fq     the same on every group of 32..256 consecutive elements of a row (k_pg.hip)
   per_group_observe_mse    per_group_observe_fq with each group's range shrunk to its least error (k_pg_mse.hip)
+  per_group_rot_observe_fq per_group_observe_fq between two Hadamard transforms of every group (k_rot.hip)
   FakeQuantFixedFn         autograd of uniform.py:55,95 with fixed qparams (STE)
   FakeQuantLearnFn         autograd of uniform.py:47-56 (LSQ: ScaleGradient, STE) (K4)
   FakeQuantLearnMultiFn    FakeQuantLearnFn over many tensors in one launch each way
@@ -1315,6 +1316,169 @@ class PerGroupLearnFn(torch.autograd.Function):
         gs = _qparam_grad(gs, s, ctx.needs_input_grad[1])
         gz = _qparam_grad(gz, z, learn_zp and ctx.needs_input_grad[2])
         return gx, gs, gz, None, None, None, None, None
+
+
+# --------------------------------------------------------------------------- per-group, Hadamard-rotated
+def _rot_view(x, group):
+    """_pg_view of x, or ValueError: a Hadamard block has no short form, so every row must be
+    whole groups."""
+    rows, rowlen, ngr = _pg_view(x, group)
+    if rowlen % group:
+        raise ValueError(f"Hadamard-rotated group-wise quantization: rowlen = {rowlen} is not a multiple of "
+                         f"G = {group}")
+    return rows, rowlen, ngr
+
+
+def _hadamard(x, group_size, what="x"):
+    group = check_group_size(group_size)
+    x, host = _pg_input(x, what)
+    rows, rowlen, _ = _rot_view(x, group)
+    if host:
+        return _host.pg_hadamard(x, group)
+    y = torch.empty_like(x)
+    rc = H.lib().vsiq_pg_hadamard_f32(H.ptr(x), H.ptr(y), _i64(rows), _i64(rowlen), _i64(group), H.stream_of(x.device))
+    H.check(rc, "vsiq_pg_hadamard_f32")
+    return y
+
+
+class _HadamardFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, group_size):
+        ctx.group = group_size
+        return _hadamard(x, group_size)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return _hadamard(gy, ctx.group, "grad_output"), None   # the matrix is symmetric
+
+
+def hadamard_transform(x: torch.Tensor, group_size: int):
+    """hadamard_G (include/vsiq.h) of every group of ``group_size`` consecutive elements of a row
+    of per_group_observe_fq's view, whose row length must be a multiple of it: the orthonormal
+    fast Walsh-Hadamard transform in natural order, one launch of csrc/k_rot.hip (CPU tensors:
+    the host loop; the same bits).  Differentiable; its backward is itself."""
+    if isinstance(x, torch.Tensor) and x.requires_grad and torch.is_grad_enabled():
+        return _HadamardFn.apply(x, group_size)
+    return _hadamard(x, group_size)
+
+
+def per_group_rot_observe_fq(x: torch.Tensor, *, group_size: int, symmetric: bool, qmin: int, qmax: int,
+                             obs_bits: int = 8, eps: float = 1e-8, run_min=None, run_max=None,
+                             quantize: bool = True, want_mask: bool = False, want_codes: bool = False,
+                             want_rotated: bool = False):
+    """per_group_observe_fq on the Hadamard-rotated groups, rotated back, in one launch and one
+    read of x (csrc/k_rot.hip): with r = hadamard_transform(x), the running state, the qparams,
+    the mask and the codes are per_group_observe_fq(r)'s, and y = hadamard_transform(of its y).
+    Bit for bit that three-launch composition.  The row length must be a multiple of
+    ``group_size`` (ValueError).
+
+    Returns per_group_observe_fq's dict plus yr: with ``want_rotated`` the fake-quantized r, the
+    rotated-domain weight a deployment stores (the codes are its codes), else None.  A CPU tensor
+    composes the host loops (byte mask, no codes)."""
+    group = check_group_size(group_size)
+    x, host = _pg_input(x)
+    rows, rowlen, ngr = _rot_view(x, group)
+    if host:
+        if want_codes:
+            raise NotImplementedError("per_group_rot_observe_fq: integer codes are written by the HIP kernel only; "
+                                      "the host loops have none")
+        r = _host.pg_observe_fq(_host.pg_hadamard(x, group), group, symmetric=symmetric, qmin=qmin, qmax=qmax,
+                                obs_bits=obs_bits, eps=eps, run_min=run_min, run_max=run_max, quantize=quantize,
+                                want_mask=want_mask)
+        q = r["y"]
+        r["yr"] = q if (want_rotated and quantize) else None
+        r["y"] = _host.pg_hadamard(q, group) if quantize else None
+        return r
+    dev = x.device
+    run_min, run_max, y, scale, zp = H.pg_observe_buffers(x, rows, ngr, run_min, run_max, quantize)
+    yr = torch.empty_like(x) if (want_rotated and quantize) else None
+    mask = H.mask_buffer(rows, rowlen, dev) if (want_mask and quantize) else None
+    codes = H.codes_buffer(x.shape, qmin, dev) if (want_codes and quantize) else None
+    rc = H.lib().vsiq_pg_rot_observe_fq_f32(H.ptr(x), H.ptr(y), H.ptr(yr), H.ptr(codes), H.ptr(mask), _i64(rows),
+                                            _i64(rowlen), _i64(group), H.ptr(run_min), H.ptr(run_max), H.ptr(scale),
+                                            H.ptr(zp), int(bool(symmetric)), int(qmin), int(qmax),
+                                            qden(symmetric, obs_bits, eps), float(eps), H.stream_of(dev))
+    H.check(rc, "vsiq_pg_rot_observe_fq_f32")
+    return dict(y=y, yr=yr, scale=scale, zp=zp, run_min=run_min, run_max=run_max, mask=mask, codes=codes)
+
+
+def per_group_rot_fake_quant(x, scale, zp, qmin, qmax, *, group_size, zp_round=False, want_mask=False,
+                             want_codes=False, want_rotated=False):
+    """per_group_fake_quant on the Hadamard-rotated groups, rotated back, in one launch: the given
+    [rows, ngr] qparams quantize hadamard_transform(x).  Returns (y, mask | None, codes | None,
+    yr | None), yr as per_group_rot_observe_fq's.  A CPU tensor composes the host loops."""
+    group = check_group_size(group_size)
+    x, host = _pg_input(x)
+    rows, rowlen, ngr = _rot_view(x, group)
+    s = _pg_f64(scale, rows, ngr, x.device, "scale")
+    z = _pg_f64(zp, rows, ngr, x.device, "zero point")
+    if host:
+        if want_codes:
+            raise NotImplementedError("per_group_rot_fake_quant: integer codes are written by the HIP kernel only; "
+                                      "the host loops have none")
+        q, mask = _host.pg_fake_quant(_host.pg_hadamard(x, group), s, z, group, qmin, qmax, zp_round=zp_round,
+                                      want_mask=want_mask)
+        return _host.pg_hadamard(q, group), mask, None, (q if want_rotated else None)
+    dev = x.device
+    y = torch.empty_like(x)
+    yr = torch.empty_like(x) if want_rotated else None
+    mask = H.mask_buffer(rows, rowlen, dev) if want_mask else None
+    codes = H.codes_buffer(x.shape, qmin, dev) if want_codes else None
+    rc = H.lib().vsiq_pg_rot_fq_fwd_f32(H.ptr(x), H.ptr(y), H.ptr(yr), H.ptr(codes), H.ptr(mask), _i64(rows),
+                                        _i64(rowlen), _i64(group), H.ptr(s), H.ptr(z), int(bool(zp_round)), int(qmin),
+                                        int(qmax), H.stream_of(dev))
+    H.check(rc, "vsiq_pg_rot_fq_fwd_f32")
+    return y, mask, codes, yr
+
+
+def pg_rot_ste_backward(g, mask, scale, group_size):
+    """The backward of the rotated forwards under the straight-through rule, one launch:
+    gx = hadamard(pg_ste_backward(hadamard(g), mask, scale)), the forward's exact adjoint."""
+    group = check_group_size(group_size)
+    g, host = _pg_input(g, "grad_output")
+    rows, rowlen, ngr = _rot_view(g, group)
+    s = _pg_f64(scale, rows, ngr, g.device, "scale")
+    if host:
+        return _host.pg_hadamard(_host.pg_ste_backward(_host.pg_hadamard(g, group), mask, s, group), group)
+    gx = torch.empty_like(g)
+    rc = H.lib().vsiq_pg_rot_ste_bwd_f32(H.ptr(g), H.ptr(mask), H.ptr(gx), _i64(rows), _i64(rowlen), _i64(group),
+                                         H.ptr(s), H.stream_of(g.device))
+    H.check(rc, "vsiq_pg_rot_ste_bwd_f32")
+    return gx
+
+
+class PerGroupRotObserveFQFn(torch.autograd.Function):
+    """per_group_rot_observe_fq with pg_rot_ste_backward.  Returns (y, scale, zp)."""
+
+    @staticmethod
+    def forward(ctx, x, group_size, symmetric, qmin, qmax, obs_bits, eps, run_min, run_max):
+        r = per_group_rot_observe_fq(x, group_size=group_size, symmetric=symmetric, qmin=qmin, qmax=qmax,
+                                     obs_bits=obs_bits, eps=eps, run_min=run_min, run_max=run_max, want_mask=True)
+        ctx.save_for_backward(r["mask"], r["scale"])
+        ctx.group = group_size
+        ctx.mark_non_differentiable(r["scale"], r["zp"])
+        return r["y"], r["scale"], r["zp"]
+
+    @staticmethod
+    def backward(ctx, gy, _gs, _gz):
+        mask, scale = ctx.saved_tensors
+        return pg_rot_ste_backward(gy, mask, scale, ctx.group), None, None, None, None, None, None, None, None
+
+
+class PerGroupRotFQFn(torch.autograd.Function):
+    """per_group_rot_fake_quant with pg_rot_ste_backward."""
+
+    @staticmethod
+    def forward(ctx, x, scale, zp, qmin, qmax, group_size):
+        y, mask, _, _ = per_group_rot_fake_quant(x, scale, zp, qmin, qmax, group_size=group_size, want_mask=True)
+        ctx.save_for_backward(mask, scale.detach().to(x.device, torch.float64))
+        ctx.group = group_size
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        mask, scale = ctx.saved_tensors
+        return pg_rot_ste_backward(gy, mask, scale, ctx.group), None, None, None, None, None
 
 
 # --------------------------------------------------------------------------- export

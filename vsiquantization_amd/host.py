@@ -353,6 +353,17 @@ def pg_lsq_backward(g, x, scale, zp, group, qmin, qmax, gscale, learn_zp):
     return gx, gs, gz
 
 
+def pg_hadamard(x, group):
+    """Host counterpart of fakequant.hadamard_transform (which has checked ``group`` and the row
+    length): hadamard_G of every group as the definition's loops."""
+    x = _f32(x)
+    rows, rowlen = _rows(x)
+    y = torch.empty_like(x)
+    rc = H.lib().vsiq_host_pg_hadamard_f32(H.ptr(x), H.ptr(y), _i64(rows), _i64(rowlen), _i64(group))
+    H.check(rc, "vsiq_host_pg_hadamard_f32")
+    return y
+
+
 def pc_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, axis=0):
     """Host counterpart of fakequant.pc_lsq_backward (``axis`` 0: [C, ...] weights, 1:
     [N, C, ...] activations -- LSQFakeQuantize): each row the per-tensor learnable host

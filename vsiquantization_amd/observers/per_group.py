@@ -11,6 +11,9 @@ sync).  CPU tensors take the native host loops group by group: the same bits.
 
 Weights only, fp32 only (PerGroupLSQQuantizer learns the qparams observed here); it is deliberately NOT a
 PerChannelMinMaxObserver, so none of the per-channel kernels' branches take it.
+With ``rotate`` set -- QuantizationManager sets it from RotatedPerGroupQuantizer's, as it keeps
+``group_size`` in step -- the observer sees every group after its Hadamard transform (csrc/k_rot.hip,
+fakequant.per_group_rot_observe_fq): the running state and the qparams are the rotated groups'.
 PerGroupMSEObserver (per_group_mse.py) subclasses it: the same view, state and protocol with every
 group's range shrunk to its least quantization error, and QuantizationManager's group-wise branch
 takes it through the two entry points below (``observe``, ``observe_quantize``).
@@ -19,7 +22,8 @@ from __future__ import annotations
 
 import torch
 
-from ..fakequant import PerGroupObserveFQFn, check_group_size, per_group_observe_fq
+from ..fakequant import (PerGroupObserveFQFn, PerGroupRotObserveFQFn, check_group_size, per_group_observe_fq,
+                         per_group_rot_observe_fq)
 from ..utils.registry import register_class
 from .base import BaseObserver
 
@@ -35,6 +39,7 @@ class PerGroupMinMaxObserver(BaseObserver):
         self.eps = eps
         self.num_bits = num_bits
         self._group_size = check_group_size(group_size)
+        self._rotate = False
         self.run_min = None   # fp32 [rows, groups] on the tensor's device
         self.run_max = None
         self.scale = None     # f64 [rows, groups] from the last observe
@@ -50,6 +55,19 @@ class PerGroupMinMaxObserver(BaseObserver):
         if g != self._group_size:
             self._group_size = g
             self.reset()   # the running state is per group
+
+    @property
+    def rotate(self) -> bool:
+        """Observe the Hadamard-rotated groups (RotatedPerGroupQuantizer; QuantizationManager keeps
+        it in step with the quantizer's, as group_size)."""
+        return self._rotate
+
+    @rotate.setter
+    def rotate(self, on):
+        on = bool(on)
+        if on != self._rotate:
+            self._rotate = on
+            self.reset()   # the running state is of the rotated or of the raw groups
 
     # ------------------------------------------------------------------ state
     @property
@@ -82,8 +100,9 @@ class PerGroupMinMaxObserver(BaseObserver):
     def observe(self, x):
         x = self._check(x).detach()
         mn, mx = self._state(x)
-        r = per_group_observe_fq(x, group_size=self._group_size, symmetric=self.symmetric, qmin=0, qmax=0,
-                                 obs_bits=self.num_bits, eps=self.eps, run_min=mn, run_max=mx, quantize=False)
+        fn = per_group_rot_observe_fq if self._rotate else per_group_observe_fq
+        r = fn(x, group_size=self._group_size, symmetric=self.symmetric, qmin=0, qmax=0, obs_bits=self.num_bits,
+               eps=self.eps, run_min=mn, run_max=mx, quantize=False)
         self.scale, self.zero_point = r["scale"], r["zp"]
 
     def get_scale_zero_point(self):
@@ -103,11 +122,13 @@ class PerGroupMinMaxObserver(BaseObserver):
         mn, mx = self._state(x)
         args = dict(group_size=self._group_size, symmetric=self.symmetric, qmin=quantizer.qmin, qmax=quantizer.qmax,
                     obs_bits=self.num_bits, eps=self.eps, run_min=mn, run_max=mx)
+        fn, fused = ((PerGroupRotObserveFQFn, per_group_rot_observe_fq) if self._rotate
+                     else (PerGroupObserveFQFn, per_group_observe_fq))
         if x.requires_grad and torch.is_grad_enabled():
-            y, s, z = PerGroupObserveFQFn.apply(x, args["group_size"], args["symmetric"], args["qmin"], args["qmax"],
-                                                args["obs_bits"], args["eps"], mn, mx)
+            y, s, z = fn.apply(x, args["group_size"], args["symmetric"], args["qmin"], args["qmax"],
+                               args["obs_bits"], args["eps"], mn, mx)
         else:
-            r = per_group_observe_fq(x, **args)
+            r = fused(x, **args)
             y, s, z = r["y"], r["scale"], r["zp"]
         self.scale, self.zero_point = s, z
         return y

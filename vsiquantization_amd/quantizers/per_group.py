@@ -17,7 +17,8 @@ from __future__ import annotations
 
 import torch
 
-from ..fakequant import PerGroupFQFn, PerGroupLearnFn, _pg_view, check_group_size, per_group_fake_quant
+from ..fakequant import (PerGroupFQFn, PerGroupLearnFn, PerGroupRotFQFn, _pg_view, check_group_size,
+                         per_group_fake_quant, per_group_rot_fake_quant)
 from ..utils.registry import register_class
 from .base import BaseQuantizer
 
@@ -28,6 +29,8 @@ class PerGroupUniformQuantizer(BaseQuantizer):
     learns_zero_point = False
     #: QuantizationManager / FakeQuantize: refused as an activation quantizer
     weights_only = True
+    #: every group is Hadamard-rotated before and after quantization (RotatedPerGroupQuantizer)
+    rotate = False
 
     def __init__(self, num_bits=8, symmetric=True, group_size=128):
         self.num_bits = num_bits
@@ -47,20 +50,22 @@ class PerGroupUniformQuantizer(BaseQuantizer):
         self._group_size = check_group_size(g)
 
     def quantize(self, x, scale, zero_point, is_learning_scale=False, act=None):
+        name = type(self).__name__ if self.rotate else "PerGroupUniformQuantizer"
         if act is not None:
-            raise NotImplementedError("PerGroupUniformQuantizer quantizes weights only: it takes no activation")
+            raise NotImplementedError(f"{name} quantizes weights only: it takes no activation")
         if is_learning_scale:
-            raise NotImplementedError("PerGroupUniformQuantizer has no learnable group scales (is_learning_scale): "
+            raise NotImplementedError(f"{name} has no learnable group scales (is_learning_scale): "
                                       "its qparams come from PerGroupMinMaxObserver")
         if not isinstance(x, torch.Tensor) or x.dtype != torch.float32:
             what = x.dtype if isinstance(x, torch.Tensor) else type(x).__name__
-            raise TypeError(f"PerGroupUniformQuantizer: only float32 tensors are supported, got {what}")
+            raise TypeError(f"{name}: only float32 tensors are supported, got {what}")
         if not (isinstance(scale, torch.Tensor) and isinstance(zero_point, torch.Tensor)):
-            raise RuntimeError("PerGroupUniformQuantizer.quantize needs the [rows, groups] scale and zero point "
+            raise RuntimeError(f"{name}.quantize needs the [rows, groups] scale and zero point "
                                "PerGroupMinMaxObserver returns (nothing observed yet?)")
+        fn, fq = (PerGroupRotFQFn, per_group_rot_fake_quant) if self.rotate else (PerGroupFQFn, per_group_fake_quant)
         if x.requires_grad and torch.is_grad_enabled():
-            return PerGroupFQFn.apply(x, scale, zero_point, self.qmin, self.qmax, self._group_size)
-        return per_group_fake_quant(x, scale, zero_point, self.qmin, self.qmax, group_size=self._group_size)[0]
+            return fn.apply(x, scale, zero_point, self.qmin, self.qmax, self._group_size)
+        return fq(x, scale, zero_point, self.qmin, self.qmax, group_size=self._group_size)[0]
 
     def __repr__(self):
         return (f"{type(self).__name__}(num_bits={self.num_bits}, symmetric={self.symmetric}, "
@@ -107,3 +112,20 @@ class PerGroupLSQQuantizer(PerGroupUniformQuantizer):
                                         zp_round=learn_zp)[0]
         gscale = float((self.qmax * G) ** -0.5)
         return PerGroupLearnFn.apply(x, scale, zero_point, self.qmin, self.qmax, gscale, learn_zp, G)
+
+
+@register_class
+class RotatedPerGroupQuantizer(PerGroupUniformQuantizer):
+    """PerGroupUniformQuantizer on Hadamard-rotated groups: y = Q(w H) H with H the orthonormal
+    Hadamard matrix of one group (include/vsiq.h hadamard_G), so an outlier is spread over its
+    group instead of setting the group's scale -- the incoherence step of QuIP# / QuaRot.  As a
+    fake quantizer it changes nothing else in a model: y is used with the raw activations, the
+    arithmetic a deployment computes with rotated activations and the rotated-domain weight.
+    One launch each way (csrc/k_rot.hip; CPU tensors: the host loops).
+
+    Used with PerGroupMinMaxObserver, which QuantizationManager switches to observing the rotated
+    groups; the [rows, groups] qparams are those of the rotated weight.  Every row must be whole
+    groups: a layer whose in_features (conv: in_channels * kh * kw) is not a multiple of
+    ``group_size`` raises ValueError at its first call.  No learnable scales, no MSE search, no
+    activations, no packed export, no AdaRound."""
+    rotate = True

@@ -19,6 +19,8 @@ MI355X differences (behaviour-preserving):
 * PerGroupMinMaxObserver + PerGroupUniformQuantizer (group-wise weights, "w4 g128") have one
   branch of their own (``_quantize_per_group``): the same one-kernel observe+quantize while
   observing, the fixed group-wise forward in eval; everything else about them is refused.
+  RotatedPerGroupQuantizer in the quantizer's place takes the same branch with every group
+  Hadamard-rotated before and after (csrc/k_rot.hip); the observer's ``rotate`` follows it.
   PerGroupLSQQuantizer in the quantizer's place adds learnable [rows, groups] qparams
   (``is_learning_scale`` / ``make_learn_qparameter``); packed export and AdaRound stay refused.
 """
@@ -528,6 +530,11 @@ class QuantizationManager(nn.Module):
         # manager observes per call under it, as the per-channel observers do
         if obs.group_size != q.group_size:   # the quantizer's is the one users set
             obs.group_size = q.group_size
+        if q.rotate and type(obs) is not PerGroupMinMaxObserver:
+            raise NotImplementedError(f"{type(q).__name__} with {type(obs).__name__}: rotated groups are observed "
+                                      "by PerGroupMinMaxObserver only")
+        if obs.rotate != q.rotate:
+            obs.rotate = q.rotate
         return obs, q
 
     def _quantize_per_group(self, x, act):
