@@ -561,6 +561,45 @@ int vsiq_pg_rot_fq_fwd_f32(const float *x, float *y, float *yr, void *codes, uin
                            int qmin, int qmax, void *stream);
 int vsiq_pg_rot_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t rows, int64_t rowlen,
                             int64_t group, const double *scale, void *stream);
+/*
+ * GPTQ for group-wise weights (Frantar et al. 2022; csrc/k_gptq.hip; added within ABI 13: purely
+ * additive): rounding with error compensation.  A row's columns are quantized in order, and after
+ * each column its rounding error is pushed onto the columns not yet quantized.
+ *
+ * w: fp32 [rows, rowlen], K3's view.  U: fp32 [rowlen, rowlen], the UPPER Cholesky factor of the
+ * damped inverse Hessian of the layer's inputs; only U[i, j] with j >= i enters a result.  group G
+ * in {32, 64, 128} with rowlen % G == 0.  symmetric, qmin, qmax, qden, eps as
+ * vsiq_pg_observe_fq_f32.  For every row r independently, with v[0 .. rowlen) an fp32 copy of the
+ * row, for i = 0 .. rowlen - 1 in order:
+ *   1. if i % G == 0: (scale, zp)[r, i / G] are the f64 qparams vsiq_pg_observe_fq_f32 gives a
+ *      FRESH group holding v[i .. i + G), the current values: lo = min(0, the group's min),
+ *      hi = max(0, its max) with strict fp32 compares, (0, 0) when the group holds a NaN, then
+ *      minmax_qparams(lo, hi) (the observer's f64 arithmetic and Python round());
+ *   2. q = the element function of vsiq_pg_fq_fwd_f32 on v[i] with those qparams;
+ *      y[r, i] = q's value, codes[r, i] = its code byte;
+ *   3. e = (v[i] - y[r, i]) / U[i, i]: one fp32 subtraction, one correctly rounded fp32 division;
+ *   4. for every j > i: v[j] = fmaf(-e, U[i, j], v[j]), one fused multiply-add.
+ * Every v[j] receives its updates as single fmaf's in ascending i, so any blocked schedule returns
+ * the bits of this loop: the device entry and vsiq_host_pg_gptq_f32 agree bit for bit in y,
+ * scale and zp.  No loop bound or address depends on the data; non-finite inputs give non-finite
+ * outputs and nothing else.
+ *
+ * Outputs: y fp32 like w (y == w is allowed), scale_out / zp_out f64 [rows, rowlen / G], codes
+ * (NULLABLE) in vsiq_pg_fq_fwd_f32's layout.  work: vsiq_pg_gptq_work_bytes(rows, rowlen) bytes of
+ * device memory of the caller's (the [rows, 128] fp32 strip of a block's errors; 0 for sizes the
+ * entry refuses); its contents after the call are unspecified.
+ * The call enqueues 2 * ceil(rowlen / 128) - 1 launches on `stream`: for every block of 128
+ * columns a block kernel and, while columns remain, a trailing kernel.  Their order is stream
+ * order alone: no workgroup waits on another, no atomics, no allocation, no synchronisation:
+ * capturable into a HIP graph.
+ * VSIQ_E_ARG: a group outside {32, 64, 128}, rowlen % group != 0, qmin > qmax, a NULL among w, U,
+ * y, scale_out, zp_out, work, rows <= 0 or rowlen <= 0, rows > 2^31 - 1, rowlen > 2^24.
+ * VSIQ_E_ALIGN: w, U, y or work not 16-byte aligned, codes not 4-byte aligned.  fp32 only.
+ */
+int64_t vsiq_pg_gptq_work_bytes(int64_t rows, int64_t rowlen);
+int vsiq_pg_gptq_f32(const float *w, const float *U, float *y, void *codes, double *scale_out, double *zp_out,
+                     void *work, int64_t rows, int64_t rowlen, int64_t group, int symmetric, int qmin, int qmax,
+                     double qden, double eps, void *stream);
 
 /*
  * Learnable (LSQ) backward (K4): grad_x plus the scale / zero-point gradients.
@@ -1120,6 +1159,11 @@ int vsiq_host_pg_lsq_bwd_f32(const float *g, const float *x, float *gx, int64_t 
  * rowlen % group != 0: VSIQ_E_ARG).  The rotated forwards and backward on CPU tensors are this
  * call around the vsiq_host_pg_* calls above. */
 int vsiq_host_pg_hadamard_f32(const float *x, float *y, int64_t rows, int64_t rowlen, int64_t group);
+/* vsiq_pg_gptq_f32 on the host: its definition as the unblocked loop, rows on the host pool
+ * (the same bits in y, scale and zp; no codes, no workspace, no alignment demands; y == w
+ * allowed).  VSIQ_E_ARG as the device entry. */
+int vsiq_host_pg_gptq_f32(const float *w, const float *U, float *y, double *scale_out, double *zp_out, int64_t rows,
+                          int64_t rowlen, int64_t group, int symmetric, int qmin, int qmax, double qden, double eps);
 /* Per-channel along axis 1 ([N, C, ...] activations, LSQFakeQuantize's broadcast of
  * [1, C, 1, ...] parameters, quantizers/lsq_module.py:141-143) on the host, in the device
  * ABI's vsiq_pcm_* layout: rows = N * channels rows of rowlen elements, row r in channel

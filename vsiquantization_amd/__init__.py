@@ -48,11 +48,13 @@ from .utils.export import export_packed_state, packed_state_weights  # noqa: F40
 from .fakequant import adaround_backward, adaround_forward  # noqa: F401
 from .quantizers.adaround import AdaRoundWeight  # noqa: F401
 from .utils.adaround import adaround_layer, adaround_model  # noqa: F401
+from .utils.gptq import gptq_factor, gptq_hessian, gptq_layer, gptq_model  # noqa: F401
 from .fakequant import mx_dequant, mx_fake_quant  # noqa: F401
 from .fakequant import per_group_fake_quant, per_group_observe_fq, pg_ste_backward  # noqa: F401
 from .fakequant import PerGroupLearnFn, pg_lsq_backward  # noqa: F401
 from .fakequant import per_group_observe_mse  # noqa: F401
 from .fakequant import hadamard_transform, per_group_rot_fake_quant, per_group_rot_observe_fq  # noqa: F401
+from .fakequant import per_group_gptq  # noqa: F401
 from .fakequant import pg_rot_ste_backward  # noqa: F401
 from .quantizers.mx import MXQuantizer  # noqa: F401
 from .utils.quantize_manager import (disable_model_launches, enable_model_launches,  # noqa: F401

@@ -25,6 +25,7 @@
 
 #include "host_simd.h"
 #include "k_adaround.cuh"
+#include "k_gptq.cuh"
 #include "k_mx.cuh"
 #include "k_observe_hist.cuh"
 #include "k_observe_mse.cuh"
@@ -802,6 +803,39 @@ int vsiq_host_pg_hadamard_f32(const float *x, float *y, int64_t rows, int64_t ro
     }
     return 0;
   });
+}
+
+// GPTQ for group-wise weights (vsiq_pg_gptq_f32's definition, include/vsiq.h) as its unblocked
+// loop: rows on the pool, a row's columns in order, every update one fmaf.  The group's qparams
+// come from k_gptq.cuh's shared range / qparam code, the element from fq() above.
+int vsiq_host_pg_gptq_f32(const float *w, const float *U, float *y, double *scale_out, double *zp_out, int64_t rows,
+                          int64_t rowlen, int64_t group, int symmetric, int qmin, int qmax, double qden, double eps) {
+  if (!gptq_sizes_ok(rows, rowlen, group) || qmin > qmax || !w || !U || !y || !scale_out || !zp_out)
+    return VSIQ_E_ARG;
+  const int64_t ngr = rowlen / group;
+  Pool::get().run(rows, [&](int64_t r) {
+    std::vector<float> v(w + r * rowlen, w + (r + 1) * rowlen);
+    HQP p{};
+    for (int64_t i = 0; i < rowlen; ++i) {
+      if (i % group == 0) {
+        GptqRange g;
+        for (int64_t j = i; j < i + group; ++j) gptq_range_add(g, v[j]);
+        double s, z;
+        gptq_group_qparams(g, symmetric, qden, eps, &s, &z);
+        scale_out[r * ngr + i / group] = s;
+        zp_out[r * ngr + i / group] = z;
+        p = make_hqp(s, z, 0, qmin, qmax);
+      }
+      bool m;
+      uint8_t c;
+      const float q = fq(v[i], p, 0, &m, &c);
+      y[r * rowlen + i] = q;
+      const float ne = -((v[i] - q) / U[i * rowlen + i]);
+      const float *u = U + i * rowlen;
+      for (int64_t j = i + 1; j < rowlen; ++j) v[j] = __builtin_fmaf(ne, u[j], v[j]);
+    }
+  });
+  return 0;
 }
 
 // Axis 1 ([N, C, ...]): row r = n * channels + c in channel c, each row the per-tensor host

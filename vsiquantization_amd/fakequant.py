@@ -1318,6 +1318,58 @@ class PerGroupLearnFn(torch.autograd.Function):
         return gx, gs, gz, None, None, None, None, None
 
 
+# --------------------------------------------------------------------------- per-group, GPTQ
+GPTQ_GROUPS = (32, 64, 128)   # group sizes of vsiq_pg_gptq_f32: the divisors of its 128-column block
+
+
+def per_group_gptq(w: torch.Tensor, U: torch.Tensor, *, group_size: int, symmetric: bool, qmin: int, qmax: int,
+                   obs_bits: int = 8, eps: float = 1e-8, want_codes: bool = False):
+    """GPTQ (Frantar et al. 2022) on per_group_observe_fq's view of ``w``: every row's columns are
+    quantized in order, each group's min/max qparams taken from the group's CURRENT values when its
+    first column comes up, and after each column its rounding error is pushed onto the columns not
+    yet quantized through ``U``, the fp32 [rowlen, rowlen] upper Cholesky factor of the damped
+    inverse Hessian of the layer's inputs (utils.gptq.gptq_factor; only its upper triangle is used).
+    include/vsiq.h (vsiq_pg_gptq_f32) states the arithmetic.  CUDA tensors run the block / trailing
+    kernels of csrc/k_gptq.hip (2 * ceil(rowlen / 128) - 1 launches), CPU tensors the host loop
+    (host.pg_gptq): the same bits.
+
+    ``group_size`` 32 / 64 / 128 and rowlen a multiple of it (ValueError); fp32 only (TypeError).
+    Returns dict(y, scale f64[rows, rowlen / G], zp f64[rows, rowlen / G], codes | None); the host
+    loop has no codes."""
+    group = check_group_size(group_size)
+    if group not in GPTQ_GROUPS:
+        raise ValueError(f"per_group_gptq: group_size must be one of {GPTQ_GROUPS}, got {group}")
+    w, host = _pg_input(w, "w")
+    rows, rowlen, ngr = _pg_view(w, group)
+    if rowlen % group:
+        raise ValueError(f"per_group_gptq: rowlen = {rowlen} is not a multiple of G = {group}")
+    if not isinstance(U, torch.Tensor):
+        raise TypeError(f"U must be a torch.Tensor, got {type(U).__name__}")
+    if U.dtype != torch.float32:
+        raise TypeError(f"per_group_gptq: U must be float32, got {U.dtype}")
+    if tuple(U.shape) != (rowlen, rowlen) or U.device != w.device:
+        raise ValueError(f"per_group_gptq: U must be a [{rowlen}, {rowlen}] tensor on {w.device} (rowlen = {rowlen}), "
+                         f"got {list(U.shape)} on {U.device}")
+    U = U.detach().contiguous()
+    w = w.detach()
+    if host:
+        if want_codes:
+            raise NotImplementedError("per_group_gptq: integer codes are written by the HIP kernel only; "
+                                      "the host loops have none")
+        return _host.pg_gptq(w, U, group, symmetric=symmetric, qmin=qmin, qmax=qmax, obs_bits=obs_bits, eps=eps)
+    dev = w.device
+    y = torch.empty_like(w)
+    scale = torch.empty(rows, ngr, dtype=torch.float64, device=dev)
+    zp = torch.empty_like(scale)
+    codes = H.codes_buffer(w.shape, qmin, dev) if want_codes else None
+    work = torch.empty(int(H.lib().vsiq_pg_gptq_work_bytes(_i64(rows), _i64(rowlen))), dtype=torch.uint8, device=dev)
+    rc = H.lib().vsiq_pg_gptq_f32(H.ptr(w), H.ptr(U), H.ptr(y), H.ptr(codes), H.ptr(scale), H.ptr(zp), H.ptr(work),
+                                  _i64(rows), _i64(rowlen), _i64(group), int(bool(symmetric)), int(qmin), int(qmax),
+                                  qden(symmetric, obs_bits, eps), float(eps), H.stream_of(dev))
+    H.check(rc, "vsiq_pg_gptq_f32")
+    return dict(y=y, scale=scale, zp=zp, codes=codes)
+
+
 # --------------------------------------------------------------------------- per-group, Hadamard-rotated
 def _rot_view(x, group):
     """_pg_view of x, or ValueError: a Hadamard block has no short form, so every row must be

@@ -364,6 +364,22 @@ def pg_hadamard(x, group):
     return y
 
 
+def pg_gptq(w, U, group, *, symmetric, qmin, qmax, obs_bits=8, eps=1e-8):
+    """Host counterpart of fakequant.per_group_gptq (which has checked ``group``, the row length
+    and ``U``): the definition's unblocked loop, rows on the host pool.  The device function's
+    dict (no codes)."""
+    w = _f32(w)
+    rows, rowlen = _rows(w)
+    y = torch.empty_like(w)
+    scale = torch.empty(rows, rowlen // group, dtype=torch.float64)
+    zp = torch.empty_like(scale)
+    rc = H.lib().vsiq_host_pg_gptq_f32(H.ptr(w), H.ptr(U), H.ptr(y), H.ptr(scale), H.ptr(zp), _i64(rows),
+                                       _i64(rowlen), _i64(group), int(bool(symmetric)), int(qmin), int(qmax),
+                                       qden(symmetric, obs_bits, eps), float(eps))
+    H.check(rc, "vsiq_host_pg_gptq_f32")
+    return dict(y=y, scale=scale, zp=zp, codes=None)
+
+
 def pc_lsq_backward(g, x, scale, zp, qmin, qmax, gscale, learn_zp, axis=0):
     """Host counterpart of fakequant.pc_lsq_backward (``axis`` 0: [C, ...] weights, 1:
     [N, C, ...] activations -- LSQFakeQuantize): each row the per-tensor learnable host
