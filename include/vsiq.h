@@ -1044,15 +1044,32 @@ int vsiq_host_adaround_bwd_f32(const float *g, const float *w, const float *v, f
  * An all-zero block: scale byte 0, y = v, mask 1, codes the sign only.  A block holding a
  * NaN or an Inf: scale byte 255 and every y of the block NaN (0x7fc00000), mask 0, codes 0.
  *
- * Host entry points only (fp32 host pointers; there is no device kernel for this yet, a CUDA
- * tensor is refused by the Python layer).  Row form (vsiq_host_mx_fq_fwd_f32): x [rows,
- * rowlen] contiguous, blocks along each row; scales [rows][ceil(rowlen / 32)] =
- * vsiq_mx_blocks(rows, rowlen) bytes.  Column form (vsiq_host_mx_fq_fwd_cols_f32): x [outer,
- * channels, inner] contiguous, blocks of 32 along `channels` (an NCHW activation's channel
- * axis); scales [outer][ceil(channels / 32)][inner].  codes, scales and mask are nullable;
- * mask is one byte per element (vsiq_host_ste_bwd_f32's layout, so that call with scale 1 is
- * the backward).  VSIQ_E_ARG: an unknown fmt, a size <= 0, x or y NULL (codes / scales /
- * mask without y included).
+ * Row form (vsiq_host_mx_fq_fwd_f32, vsiq_mx_fq_fwd_f32): x [rows, rowlen] contiguous, blocks
+ * along each row; scales [rows][ceil(rowlen / 32)] = vsiq_mx_blocks(rows, rowlen) bytes.
+ * Column form (vsiq_host_mx_fq_fwd_cols_f32, vsiq_mx_fq_fwd_cols_f32): x [outer, channels,
+ * inner] contiguous, blocks of 32 along `channels` (an NCHW activation's channel axis);
+ * scales [outer][ceil(channels / 32)][inner].  codes, scales and mask are nullable.
+ * VSIQ_E_ARG: an unknown fmt, a size <= 0, x or y NULL (codes / scales / mask without y
+ * included).
+ *
+ * Host entries (fp32 host pointers): mask is one byte per element (vsiq_host_ste_bwd_f32's
+ * layout, so that call with scale 1 is the backward).
+ *
+ * Device entries (csrc/k_mx.hip; fp32 device pointers, one launch on `stream`, one read of x,
+ * no workspace: capturable into a HIP graph).  The same results as the host entries bit for
+ * bit, fp32 denormals included.  mask is the 1-bit mask stated at the top of this file, in
+ * the view
+ *   row form:     (1, rows * rowlen)           the per-tensor view, vsiq_mask_words(1, n) words
+ *   column form:  (outer * channels, inner)    vsiq_mask_words(outer * channels, inner) words
+ * and every word of it is written whole by the launch (bits past a row's end 0): nothing has
+ * to be cleared first.  vsiq_ste_bwd_f32 with scale 1 on that view -- scale_host = 1 for the
+ * row form, rowlen = inner and scale_dev = outer * channels ones for the column form -- is
+ * the backward, (mask ? g * 1 : 0) / 1.  Argument errors as the host entries', checked
+ * before anything is launched; then a mask that is not 8-byte aligned: VSIQ_E_ALIGN; more
+ * than 2^31 - 1 wave tasks (256-element chunks of the tensor; outer * channel blocks *
+ * 256-position chunks of inner): VSIQ_E_ARG.  rowlen % 4 == 0 (inner % 4 == 0) with 16-byte
+ * aligned x and y and 4-byte aligned codes (and scales, column form) takes the vector path,
+ * anything else a per-element path with the same results.
  */
 #define VSIQ_MX_FP4_E2M1 0
 #define VSIQ_MX_FP6_E2M3 1
@@ -1064,6 +1081,10 @@ int vsiq_host_mx_fq_fwd_f32(const float *x, float *y, uint8_t *codes, uint8_t *s
                             int64_t rowlen, int fmt);
 int vsiq_host_mx_fq_fwd_cols_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales, uint8_t *mask,
                                  int64_t outer, int64_t channels, int64_t inner, int fmt);
+int vsiq_mx_fq_fwd_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales, uint64_t *mask, int64_t rows,
+                       int64_t rowlen, int fmt, void *stream);
+int vsiq_mx_fq_fwd_cols_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales, uint64_t *mask,
+                            int64_t outer, int64_t channels, int64_t inner, int fmt, void *stream);
 
 /*
  * BatchNorm folding (modules/fused.py:100-108, :294-300), fp32, reference order:

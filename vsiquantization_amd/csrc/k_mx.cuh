@@ -1,6 +1,5 @@
 // k_mx.cuh — OCP Microscaling (MX v1.0) element arithmetic of the host loops (k_host.hip),
-// written __host__ __device__ so that a device kernel can share it unchanged (none is built
-// yet: DESIGN.md §7).  32 elements share one power-of-two E8M0 scale X = 2^E; each
+// written __host__ __device__ and shared unchanged by the device kernels (k_mx.hip).  32 elements share one power-of-two E8M0 scale X = 2^E; each
 // element is a 4-, 6- or 8-bit float.  Nothing here is approximate (include/vsiq.h has
 // the full statement):
 //   code(scale) = max(exp_field(amax) - emax, 0)       E = code - 127 (floor(log2 amax) - emax,

@@ -19,7 +19,7 @@ eager torch ops in the reference:
   FakeQuantLearnMultiFn    FakeQuantLearnFn over many tensors in one launch each way
   observe_parts/fold_parts deferred-calibration observer (K2p) and its one-launch fold
   observe_parts_out        K2p that also writes act(x): a fused layer's calibration forward (K2o)
-  mx_fake_quant            OCP MX block-scaled fake quant (MXFP4 / MXFP6 / MXFP8), CPU tensors only so far
+  mx_fake_quant            OCP MX block-scaled fake quant (MXFP4 / MXFP6 / MXFP8) (k_mx.hip)
 
 Every op takes an optional ``act`` ("relu" / "silu", K5): the op is then applied
 to act(x) without materializing it -- the fused layers' F.relu / F.silu before
@@ -1832,40 +1832,67 @@ def _mx_view(shape, axis):
     raise NotImplementedError(f"MX blocks run along the last axis or axis 1, got axis {axis} of a {nd}-d tensor")
 
 
+def _mx_mask_view(view):
+    """(rows, rowlen) of the device kernels' 1-bit mask (include/vsiq.h): the row form writes
+    the per-tensor view, one row of every element; the column form one row per (outer,
+    channel), so that a wave's 256 inner positions of a channel are one mask chunk."""
+    return (1, view[0] * view[1]) if len(view) == 2 else (view[0] * view[1], view[2])
+
+
 def _mx_forward(x, fmt, axis, want_codes, want_mask):
-    """One MX fake-quant call on a contiguous CPU float32 x (the host loops): (y, codes | None,
-    scales | None, mask | None); the mask is one byte per element.  There is no device kernel:
-    a CUDA tensor raises (never a quiet copy to the host)."""
+    """One MX fake-quant call on a contiguous float32 x: (y, codes | None, scales | None,
+    mask | None).  A CPU tensor runs the host loops and its mask is one byte per element; a
+    CUDA tensor is one launch of csrc/k_mx.hip on its current stream and its mask the 1-bit
+    words of ``_mx_mask_view``, every word written by that launch (nothing is cleared first).
+    Any other device or element type raises (never a quiet copy to the host)."""
     code = _mx_format(fmt)[0]
+    dev = x.device
     if not _host.is_host(x):
-        if x.device.type == "cpu":
-            raise TypeError(f"x: only float32 is supported by the host (CPU) MX fake quant, got {x.dtype}")
-        raise H.VsiqError(f"x is on {x.device}: MX fake quant has no HIP kernel yet and runs on CPU float32 "
-                          "tensors only (the native host loops); nothing is copied to the host behind your back")
+        if dev.type == "cpu" or (dev.type == "cuda" and x.dtype != torch.float32):
+            raise TypeError(f"x: only float32 is supported by the MX fake quant, got {x.dtype}")
+        if dev.type != "cuda":
+            raise H.VsiqError(f"x is on {dev}: MX fake quant has no HIP kernel for that device and runs on CUDA "
+                              "and CPU float32 tensors only; nothing is copied to the host behind your back")
     view, sshape = _mx_view(x.shape, axis)
     y = torch.empty_like(x)
-    codes = torch.empty(x.shape, dtype=torch.uint8) if want_codes else None
-    scales = torch.empty(sshape, dtype=torch.uint8) if want_codes else None
-    mask = torch.empty(x.shape, dtype=torch.uint8) if want_mask else None
-    _host.mx_fake_quant(x, y, codes, scales, mask, view, code)
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=dev) if want_codes else None
+    scales = torch.empty(sshape, dtype=torch.uint8, device=dev) if want_codes else None
+    if dev.type == "cpu":
+        mask = torch.empty(x.shape, dtype=torch.uint8) if want_mask else None
+        _host.mx_fake_quant(x, y, codes, scales, mask, view, code)
+        return y, codes, scales, mask
+    mask = H.mask_buffer(*_mx_mask_view(view), dev) if want_mask else None
+    name = "vsiq_mx_fq_fwd_f32" if len(view) == 2 else "vsiq_mx_fq_fwd_cols_f32"
+    rc = getattr(H.lib(), name)(H.ptr(x), H.ptr(y), H.ptr(codes), H.ptr(scales), H.ptr(mask), *map(_i64, view), code,
+                                H.stream_of(dev))
+    H.check(rc, name)
     return y, codes, scales, mask
 
 
 class MXFakeQuantFn(torch.autograd.Function):
     """MX fake quant with the straight-through gradient: grad_x = g where rounding stayed on
     the element grid, 0 where it picked the overflow value.  Saves the mask; the backward is
-    the existing STE backward with scale 1 ((mask ? g * 1 : 0) / 1 is g exactly)."""
+    the existing STE backward with scale 1 ((mask ? g * 1 : 0) / 1 is g exactly) on the
+    forward's mask view: on the device the per-tensor view for blocks along rows, and one row
+    per (outer, channel) -- hence one scale of 1 per row -- for blocks along the channels.
+    Calling backward() inside a HIP-graph capture is unsupported (capture the forward and
+    ste_backward separately)."""
 
     @staticmethod
     def forward(ctx, x, fmt, axis):
         y, _, _, mask = _mx_forward(x, fmt, axis, False, True)
+        ctx.view = _mx_mask_view(_mx_view(x.shape, axis)[0])
         ctx.save_for_backward(mask)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         (mask,) = ctx.saved_tensors
-        return ste_backward(gy.contiguous(), mask, 1.0), None, None
+        rows, rowlen = ctx.view
+        if gy.device.type == "cpu" or rows == 1:
+            return ste_backward(gy.contiguous(), mask, 1.0), None, None
+        ones = torch.ones(rows, dtype=torch.float64, device=gy.device)
+        return ste_backward(gy.contiguous(), mask, ones, rowlen), None, None
 
 
 def _is_channels_last(x) -> bool:
@@ -1876,8 +1903,8 @@ def mx_fake_quant(x: torch.Tensor, fmt: str, axis: int = -1, want_codes: bool = 
     """OCP MX fake quant (include/vsiq.h, "MX block-scaled fake quantization"): blocks of 32
     consecutive elements along ``axis`` share one power-of-two scale and every element is
     rounded to the 4-, 6- or 8-bit float ``fmt`` ("fp4_e2m1", "fp6_e2m3", "fp6_e3m2",
-    "fp8_e4m3", "fp8_e5m2").  CPU float32 tensors only, on the native host loops (there is no
-    HIP kernel for it yet: a CUDA tensor raises VsiqError).
+    "fp8_e4m3", "fp8_e5m2").  float32 tensors: a CUDA tensor is one launch of csrc/k_mx.hip, a
+    CPU tensor the native host loops, with the same bits (16-bit tensors raise TypeError).
     axis=-1: rows are everything before the last dim; axis=1 of an [N, C, ...] tensor: blocks
     along the channels (an [N, C] tensor: its rows).  Differentiable in x (MXFakeQuantFn).
     Returns y, or (y, codes uint8 like x, scales uint8: x's shape with ``axis`` cut to its

@@ -4,9 +4,10 @@ power-of-two E8M0 scale and each element is a 4-, 6- or 8-bit float (MXFP4 / MXF
 
 The scale comes from each block's own maximum, so there is nothing to observe and nothing to
 learn: ``self_scaled`` tells QuantizationManager to call ``quantize`` without an observer
-pass, stats records or qparams.  CPU float32 tensors only so far, on the library's native
-host loops (csrc/k_host.hip, element code csrc/k_mx.cuh); a CUDA tensor raises, there is no
-HIP kernel for it yet.  Straight-through gradient from the saved mask.
+pass, stats records or qparams.  float32 tensors: a CUDA tensor is one launch of
+csrc/k_mx.hip, a CPU tensor the library's native host loops (csrc/k_host.hip), both on the
+element code of csrc/k_mx.cuh and equal bit for bit; 16-bit tensors raise TypeError.
+Straight-through gradient from the saved mask (one bit per element on the device).
 """
 from __future__ import annotations
 
