@@ -1085,6 +1085,50 @@ int vsiq_mx_fq_fwd_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales
                        int64_t rowlen, int fmt, void *stream);
 int vsiq_mx_fq_fwd_cols_f32(const float *x, float *y, uint8_t *codes, uint8_t *scales, uint64_t *mask,
                             int64_t outer, int64_t channels, int64_t inner, int fmt, void *stream);
+/*
+ * Hadamard-rotated MX fake quantization (RotatedMXQuantizer; csrc/k_mx_rot.hip; added within ABI
+ * 13: purely additive).  Every scale block of 32 is rotated by the orthonormal Hadamard matrix
+ * before it is quantized and rotated back after, so one outlier is spread over its block instead
+ * of setting the block's scale:
+ *   yr = MX(hadamard_32(x))        the rotated-domain tensor a deployment stores
+ *   y  = hadamard_32(yr)
+ *   gx = hadamard_32(mask ? hadamard_32(g) : +0)      the straight-through backward
+ * hadamard_32 is hadamard_G above at G = 32 (stages h = 1 .. 16 in fp32, one multiply by c_32, a
+ * NaN result canonical); MX is the block arithmetic above, unchanged.  Block length equals
+ * transform length: nothing crosses a block.
+ *
+ * Layouts: the MX device entries' row form [rows, rowlen] and column form [outer, channels,
+ * inner], with ONE more restriction: rowlen % 32 == 0 (channels % 32 == 0); a Hadamard block
+ * has no short form.  y is required; yr, codes, scales and mask are nullable.  codes, scales and
+ * mask are those of the ROTATED tensor, in exactly the layouts and mask views
+ * vsiq_mx_fq_fwd_f32 / vsiq_mx_fq_fwd_cols_f32 write (every mask word written whole).
+ *
+ * Each call equals, bit for bit in every output, the composition of the existing entries:
+ *   vsiq_mx_rot_fq_fwd_f32        vsiq_pg_hadamard_f32(x, group 32) -> vsiq_mx_fq_fwd_f32 (its y
+ *                                 is yr; codes, scales, mask) -> vsiq_pg_hadamard_f32 (y)
+ *   vsiq_mx_rot_fq_fwd_cols_f32   the same on the [outer * inner, channels] transpose:
+ *                                 vsiq_mx_fq_fwd_cols_f32 of the tensor whose channel blocks were
+ *                                 transformed, then those blocks transformed again
+ *   vsiq_mx_rot_ste_bwd_f32       vsiq_pg_hadamard_f32(g) -> vsiq_ste_bwd_f32 with scale 1 on the
+ *   vsiq_mx_rot_ste_bwd_cols_f32  forward's mask view -> vsiq_pg_hadamard_f32
+ * blocks holding NaN, Inf, only zeros or fp32 denormals included.
+ *
+ * One launch each on `stream`, one read of x (g); no workspace, LDS state, atomics, allocation
+ * or synchronisation: capturable into a HIP graph.  fp32 only.  Checked before anything is
+ * launched: VSIQ_E_ARG for a size <= 0, a size product that overflows, more than 2^31 - 1 wave
+ * tasks, an unknown fmt, a NULL x / y (g / mask / gx) or a block axis that is not a multiple of
+ * 32; then VSIQ_E_ALIGN for a mask that is not 8-byte aligned.  16-byte aligned fp32 tensors
+ * (4-byte aligned codes; column form: inner % 4 == 0 and 4-byte aligned scales) take the vector
+ * path, anything else a per-element path with the same lane mapping and the same results.
+ */
+int vsiq_mx_rot_fq_fwd_f32(const float *x, float *y, float *yr, uint8_t *codes, uint8_t *scales, uint64_t *mask,
+                           int64_t rows, int64_t rowlen, int fmt, void *stream);
+int vsiq_mx_rot_fq_fwd_cols_f32(const float *x, float *y, float *yr, uint8_t *codes, uint8_t *scales, uint64_t *mask,
+                                int64_t outer, int64_t channels, int64_t inner, int fmt, void *stream);
+int vsiq_mx_rot_ste_bwd_f32(const float *g, const uint64_t *mask, float *gx, int64_t rows, int64_t rowlen,
+                            void *stream);
+int vsiq_mx_rot_ste_bwd_cols_f32(const float *g, const uint64_t *mask, float *gx, int64_t outer, int64_t channels,
+                                 int64_t inner, void *stream);
 
 /*
  * BatchNorm folding (modules/fused.py:100-108, :294-300), fp32, reference order:

@@ -14,6 +14,7 @@ Importing the package registers the quantizer/observer classes by name in
   PerGroupMSEObserver                               (PerGroupMinMaxObserver with each group's range shrunk to its least error)
   RotatedPerGroupQuantizer                          (PerGroupUniformQuantizer on Hadamard-rotated groups: y = Q(w H) H)
   MXQuantizer                                       (OCP MX block scaling: MXFP4 / MXFP6 / MXFP8)
+  RotatedMXQuantizer                                (MXQuantizer on Hadamard-rotated blocks: y = MX(x H) H)
 
 plus ``LSQFakeQuantize`` (quantizers/lsq_module.py, the torch.ao-based LSQ module).
 All fake-quant arithmetic runs in the HIP kernels of ``csrc/`` through the C ABI of
@@ -56,7 +57,8 @@ from .fakequant import per_group_observe_mse  # noqa: F401
 from .fakequant import hadamard_transform, per_group_rot_fake_quant, per_group_rot_observe_fq  # noqa: F401
 from .fakequant import per_group_gptq  # noqa: F401
 from .fakequant import pg_rot_ste_backward  # noqa: F401
-from .quantizers.mx import MXQuantizer  # noqa: F401
+from .fakequant import mx_rot_fake_quant, mx_rot_ste_backward  # noqa: F401
+from .quantizers.mx import MXQuantizer, RotatedMXQuantizer  # noqa: F401
 from .utils.quantize_manager import (disable_model_launches, enable_model_launches,  # noqa: F401
                                      model_launches_enabled)
 

@@ -317,6 +317,10 @@ _SIGS = {
     "vsiq_host_mx_fq_fwd_cols_f32": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int], c_int),
     "vsiq_mx_fq_fwd_f32": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int, c_p], c_int),
     "vsiq_mx_fq_fwd_cols_f32": ([c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p], c_int),
+    "vsiq_mx_rot_fq_fwd_f32": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_int, c_p], c_int),
+    "vsiq_mx_rot_fq_fwd_cols_f32": ([c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_int, c_p], c_int),
+    "vsiq_mx_rot_ste_bwd_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_p], c_int),
+    "vsiq_mx_rot_ste_bwd_cols_f32": ([c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p], c_int),
 }
 EXPORTED = tuple(_SIGS)
 

@@ -33,47 +33,13 @@
 //
 // The vector paths stream with nontemporal loads and stores, the per-element paths use plain
 // ones, as k_pg.hip; this file does not read the tuning knob.
-#include "k_mx.cuh"
+#include "k_mx_wave.cuh"   // the element code (k_mx.cuh), mx_quad, mx_mask_word, MxCols
 #include "k_pg_wave.cuh"   // pg_reduce
 
 namespace vsiq {
 
 constexpr int kMxSpan = 4 * kBlock;   // elements of a k_mx_rows_any workgroup
 constexpr int kMxU = 4;               // k_mx_rows32: chunks per wave where the grid still fills the device
-
-struct MxMaxBits {
-  static __device__ uint32_t identity() { return 0u; }
-  __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a > b ? a : b; }
-};
-
-__device__ __forceinline__ uint32_t mx_abs_bits(float v) { return f2u(v) & 0x7fffffffu; }
-
-// a lane's 4 elements with their scales: y, the 4 code bytes, the 4 mask bits
-struct MxQuad {
-  f4 y;
-  uint32_t c;
-  bool m[4];
-};
-
-template <bool CODES>
-__device__ __forceinline__ MxQuad mx_quad(const f4 &v, const MxScale &s0, const MxScale &s1, const MxScale &s2,
-                                          const MxScale &s3, const MxFmt &f) {
-  const MxElem a = mx_elem<CODES>(v.x, s0, f), b = mx_elem<CODES>(v.y, s1, f), c = mx_elem<CODES>(v.z, s2, f),
-               d = mx_elem<CODES>(v.w, s3, f);
-  MxQuad q;
-  q.y.x = a.y; q.y.y = b.y; q.y.z = c.y; q.y.w = d.y;
-  q.c = a.code | (b.code << 8) | (c.code << 16) | (d.code << 24);
-  q.m[0] = a.m; q.m[1] = b.m; q.m[2] = c.m; q.m[3] = d.m;
-  return q;
-}
-
-// the wave's four ballots of (m[j] and element j of the lane exists: nv of its 4 do), word j in lane j
-__device__ __forceinline__ uint64_t mx_mask_word(const bool (&m)[4], int nv) {
-  const uint64_t b0 = __ballot(m[0] && nv > 0), b1 = __ballot(m[1] && nv > 1), b2 = __ballot(m[2] && nv > 2),
-                 b3 = __ballot(m[3] && nv > 3);
-  const uint32_t lane = threadIdx.x % kWave;
-  return lane == 0 ? b0 : lane == 1 ? b1 : lane == 2 ? b2 : b3;
-}
 
 // ----------------------------------------------------------------------------
 // rows, rowlen % 32 == 0: a block is 8 adjacent lanes
@@ -191,11 +157,6 @@ __global__ __launch_bounds__(kBlock) void k_mx_rows_any(const float *__restrict_
 // ----------------------------------------------------------------------------
 // columns: lanes along inner, every lane its 4 blocks' <= 32 channels in registers
 // ----------------------------------------------------------------------------
-struct MxCols {
-  int64_t channels, inner;
-  uint32_t cb, cpr, tasks;   // channel blocks, 256-position chunks of inner, outer * cb * cpr wave tasks
-};
-
 template <bool VEC, bool CODES, bool MASK>
 __global__ __launch_bounds__(kBlock) void k_mx_cols(const float *__restrict__ x, float *__restrict__ y,
                                                     uint8_t *__restrict__ codes, uint8_t *__restrict__ scales,

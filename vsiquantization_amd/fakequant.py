@@ -20,6 +20,7 @@ eager torch ops in the reference:
   observe_parts/fold_parts deferred-calibration observer (K2p) and its one-launch fold
   observe_parts_out        K2p that also writes act(x): a fused layer's calibration forward (K2o)
   mx_fake_quant            OCP MX block-scaled fake quant (MXFP4 / MXFP6 / MXFP8) (k_mx.hip)
+  mx_rot_fake_quant        mx_fake_quant between two 32-point Hadamard transforms of every block (k_mx_rot.hip)
 
 Every op takes an optional ``act`` ("relu" / "silu", K5): the op is then applied
 to act(x) without materializing it -- the fused layers' F.relu / F.silu before
@@ -1839,6 +1840,18 @@ def _mx_mask_view(view):
     return (1, view[0] * view[1]) if len(view) == 2 else (view[0] * view[1], view[2])
 
 
+def _mx_device(x, what="x"):
+    """x's device, or the MX ops' refusal: float32 on CUDA or the CPU only."""
+    dev = x.device
+    if not _host.is_host(x):
+        if dev.type == "cpu" or (dev.type == "cuda" and x.dtype != torch.float32):
+            raise TypeError(f"{what}: only float32 is supported by the MX fake quant, got {x.dtype}")
+        if dev.type != "cuda":
+            raise H.VsiqError(f"{what} is on {dev}: MX fake quant has no HIP kernel for that device and runs on CUDA "
+                              "and CPU float32 tensors only; nothing is copied to the host behind your back")
+    return dev
+
+
 def _mx_forward(x, fmt, axis, want_codes, want_mask):
     """One MX fake-quant call on a contiguous float32 x: (y, codes | None, scales | None,
     mask | None).  A CPU tensor runs the host loops and its mask is one byte per element; a
@@ -1846,13 +1859,7 @@ def _mx_forward(x, fmt, axis, want_codes, want_mask):
     words of ``_mx_mask_view``, every word written by that launch (nothing is cleared first).
     Any other device or element type raises (never a quiet copy to the host)."""
     code = _mx_format(fmt)[0]
-    dev = x.device
-    if not _host.is_host(x):
-        if dev.type == "cpu" or (dev.type == "cuda" and x.dtype != torch.float32):
-            raise TypeError(f"x: only float32 is supported by the MX fake quant, got {x.dtype}")
-        if dev.type != "cuda":
-            raise H.VsiqError(f"x is on {dev}: MX fake quant has no HIP kernel for that device and runs on CUDA "
-                              "and CPU float32 tensors only; nothing is copied to the host behind your back")
+    dev = _mx_device(x)
     view, sshape = _mx_view(x.shape, axis)
     y = torch.empty_like(x)
     codes = torch.empty(x.shape, dtype=torch.uint8, device=dev) if want_codes else None
@@ -1949,3 +1956,111 @@ def mx_dequant(codes: torch.Tensor, scales: torch.Tensor, fmt: str, axis: int = 
     y = table[codes.long() & ((1 << bits) - 1)] * x2
     y = torch.where(nan_block, torch.full_like(y, float("nan")), y)
     return y if dtype == torch.float32 else y.to(dtype)
+
+
+# --------------------------------------------------------------------------- MX, Hadamard-rotated
+def _mx_rot_view(shape, axis):
+    """_mx_view, or ValueError: a Hadamard block has no short form, so the block axis must be
+    whole blocks of 32."""
+    view, sshape = _mx_view(shape, axis)
+    if view[1] % 32:
+        raise ValueError(f"Hadamard-rotated MX fake quant: the block axis of shape {tuple(shape)} has length "
+                         f"{view[1]}, not a multiple of 32")
+    return view, sshape
+
+
+def _mx_rot_hadamard_host(t, view):
+    """hadamard_32 of every block of a contiguous CPU tensor in the host loops' ``view``: the
+    host Hadamard loop on the blocks as rows (column form: on the transpose and back)."""
+    if len(view) == 2:
+        return _host.pg_hadamard(t.reshape(-1, 32), 32).reshape(t.shape)
+    tt = t.reshape(view).transpose(1, 2).contiguous()   # [outer, inner, channels]
+    return _host.pg_hadamard(tt.reshape(-1, 32), 32).reshape(tt.shape).transpose(1, 2).contiguous().reshape(t.shape)
+
+
+def _mx_rot_forward(x, fmt, axis, want_codes, want_mask, want_rotated=False):
+    """One rotated MX call on a contiguous float32 x: (y, yr | None, codes | None, scales | None,
+    mask | None); yr = MX(hadamard_32(x)), codes / scales / mask are its.  A CUDA tensor is one
+    launch of csrc/k_mx_rot.hip; a CPU tensor composes the existing host loops (the definition)."""
+    code = _mx_format(fmt)[0]
+    dev = _mx_device(x)
+    view, sshape = _mx_rot_view(x.shape, axis)
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=dev) if want_codes else None
+    scales = torch.empty(sshape, dtype=torch.uint8, device=dev) if want_codes else None
+    if dev.type == "cpu":
+        yr = torch.empty_like(x)
+        mask = torch.empty(x.shape, dtype=torch.uint8) if want_mask else None
+        _host.mx_fake_quant(_mx_rot_hadamard_host(x, view), yr, codes, scales, mask, view, code)
+        return _mx_rot_hadamard_host(yr, view), (yr if want_rotated else None), codes, scales, mask
+    y = torch.empty_like(x)
+    yr = torch.empty_like(x) if want_rotated else None
+    mask = H.mask_buffer(*_mx_mask_view(view), dev) if want_mask else None
+    name = "vsiq_mx_rot_fq_fwd_f32" if len(view) == 2 else "vsiq_mx_rot_fq_fwd_cols_f32"
+    rc = getattr(H.lib(), name)(H.ptr(x), H.ptr(y), H.ptr(yr), H.ptr(codes), H.ptr(scales), H.ptr(mask),
+                                *map(_i64, view), code, H.stream_of(dev))
+    H.check(rc, name)
+    return y, yr, codes, scales, mask
+
+
+def mx_rot_ste_backward(g: torch.Tensor, mask: torch.Tensor, axis: int = -1):
+    """The rotated MX forward's straight-through backward on its saved mask, in one launch:
+    gx = hadamard_32(mask ? hadamard_32(g) : 0) per block of 32 along ``axis`` of g (the forward's
+    shape and axis).  For callers who capture forward and backward separately; a CPU g composes
+    the host loops on the forward's byte mask."""
+    if not isinstance(g, torch.Tensor):
+        raise TypeError(f"grad_output must be a torch.Tensor, got {type(g).__name__}")
+    dev = _mx_device(g, "grad_output")
+    g = g.contiguous()
+    view, _ = _mx_rot_view(g.shape, axis)
+    if dev.type == "cpu":
+        return _mx_rot_hadamard_host(_host.ste_backward(_mx_rot_hadamard_host(g, view), mask, 1.0), view)
+    gx = torch.empty_like(g)
+    name = "vsiq_mx_rot_ste_bwd_f32" if len(view) == 2 else "vsiq_mx_rot_ste_bwd_cols_f32"
+    rc = getattr(H.lib(), name)(H.ptr(g), H.ptr(mask), H.ptr(gx), *map(_i64, view), H.stream_of(dev))
+    H.check(rc, name)
+    return gx
+
+
+class MXRotFakeQuantFn(torch.autograd.Function):
+    """Rotated MX fake quant with mx_rot_ste_backward.  Saves only the mask (one bit per element
+    on the device).  Calling backward() inside a HIP-graph capture is unsupported (capture the
+    forward and mx_rot_ste_backward separately)."""
+
+    @staticmethod
+    def forward(ctx, x, fmt, axis):
+        y, _, _, _, mask = _mx_rot_forward(x, fmt, axis, False, True)
+        ctx.axis = axis
+        ctx.save_for_backward(mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (mask,) = ctx.saved_tensors
+        return mx_rot_ste_backward(gy, mask, ctx.axis), None, None
+
+
+def mx_rot_fake_quant(x: torch.Tensor, fmt: str, axis: int = -1, want_codes: bool = False):
+    """mx_fake_quant between two 32-point Hadamard transforms of every scale block (include/vsiq.h,
+    "Hadamard-rotated MX fake quantization"): y = hadamard_32(MX(hadamard_32(x))), so an outlier
+    is spread over its block instead of setting the block's scale.  One launch of
+    csrc/k_mx_rot.hip and one read of x, equal bit for bit to hadamard_transform(x, 32) ->
+    mx_fake_quant -> hadamard_transform; a CPU tensor composes the host loops.  mx_fake_quant's
+    axis rules, channels-last shortcut and refusals; the block axis must be a multiple of 32
+    (ValueError).  Differentiable in x (MXRotFakeQuantFn).  ``want_codes`` returns (y, codes,
+    scales) of the ROTATED domain: hadamard_transform(mx_dequant(codes, scales, fmt), 32) is y."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"x must be a torch.Tensor, got {type(x).__name__}")
+    _mx_format(fmt)
+    nd = x.dim()
+    if nd and not -nd <= axis < nd:
+        raise NotImplementedError(f"MX blocks run along the last axis or axis 1, got axis {axis} of a {nd}-d tensor")
+    if axis % max(nd, 1) == 1 and _is_channels_last(x):   # NHWC memory: the channels are its rows
+        out = mx_rot_fake_quant(x.permute(0, 2, 3, 1), fmt, -1, want_codes)
+        return tuple(t.permute(0, 3, 1, 2) for t in out) if want_codes else out.permute(0, 3, 1, 2)
+    x = x.contiguous()
+    if want_codes:
+        y, _, codes, scales, _ = _mx_rot_forward(x.detach(), fmt, axis, True, False)
+        return y, codes, scales
+    if x.requires_grad and torch.is_grad_enabled():
+        return MXRotFakeQuantFn.apply(x, fmt, axis)
+    return _mx_rot_forward(x, fmt, axis, False, False)[0]

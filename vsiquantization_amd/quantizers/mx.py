@@ -11,7 +11,7 @@ Straight-through gradient from the saved mask (one bit per element on the device
 """
 from __future__ import annotations
 
-from ..fakequant import mx_fake_quant
+from ..fakequant import mx_fake_quant, mx_rot_fake_quant
 from ..utils.registry import register_class
 from .base import BaseQuantizer
 
@@ -24,6 +24,8 @@ class MXQuantizer(BaseQuantizer):
     #: QuantizationManager: no observer call, no stats, no qparams for this quantizer
     self_scaled = True
     learns_zero_point = False
+    #: the fake-quant function of this class: (x, elem_format, axis=, want_codes=)
+    fake_quant = staticmethod(mx_fake_quant)
 
     def __init__(self, num_bits=4, symmetric=True):
         if num_bits not in _BY_BITS:
@@ -54,7 +56,20 @@ class MXQuantizer(BaseQuantizer):
         axis = self.block_axis
         if x.dim() < 2 and axis not in (-1, x.dim() - 1):
             axis = -1   # a vector has one axis
-        return mx_fake_quant(x, self._elem_format, axis=axis)
+        return self.fake_quant(x, self._elem_format, axis=axis)
 
     def __repr__(self):
         return f"{type(self).__name__}(elem_format={self._elem_format!r}, block_axis={self.block_axis})"
+
+
+@register_class
+class RotatedMXQuantizer(MXQuantizer):
+    """MXQuantizer on Hadamard-rotated blocks: y = hadamard_32(MX(hadamard_32(x))) per scale block,
+    one launch of csrc/k_mx_rot.hip each way (CPU tensors: the host loops composed).  One outlier
+    no longer sets its block's scale -- it is spread over the 32 elements first -- and for a
+    linear layer whose weights and activations are both rotated along the contraction axis the
+    fake-quantized product equals the block-scaled product of the exported rotated-domain codes.
+    The block axis must be a multiple of 32 (ValueError); QuantizationManager.export_mx returns the
+    rotated-domain codes: hadamard_transform(mx_dequant(codes, scales, fmt), 32) reproduces y."""
+
+    fake_quant = staticmethod(mx_rot_fake_quant)

@@ -584,14 +584,15 @@ class QuantizationManager(nn.Module):
         """``x`` as MX element codes and block scales: (codes uint8 like x, scales uint8, the
         element-format name) of what ``quantize(x)`` computes under a self-scaled quantizer
         (MXQuantizer); fakequant.mx_dequant(codes, scales, fmt, axis=quantizer.block_axis)
-        reproduces it.  Nothing changes; the activation is not applied."""
+        reproduces it.  Under a RotatedMXQuantizer the codes are the rotated domain's, what a
+        block-scaled matrix unit consumes: fakequant.hadamard_transform(mx_dequant(...), 32) along
+        the block axis reproduces ``quantize(x)``.  Nothing changes; the activation is not applied."""
         q = self.quantizer
         if not getattr(q, "self_scaled", False):
             raise NotImplementedError(f"export_mx supports MXQuantizer, not {type(q).__name__}")
-        from ..fakequant import mx_fake_quant
         self._join()
         axis = q.block_axis if x.dim() >= 2 else -1
-        _, codes, scales = mx_fake_quant(x.detach(), q.elem_format, axis=axis, want_codes=True)
+        _, codes, scales = q.fake_quant(x.detach(), q.elem_format, axis=axis, want_codes=True)
         return codes, scales, q.elem_format
 
     def current_grid(self, x, what: str = "current_grid"):
